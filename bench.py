@@ -11,11 +11,21 @@ all-reduce per step (north_star): total work is fixed -> "scal
 complete N>1 path (rank launch, sharded kernels, all-reduce, MAX-reduced timings, the JSON line with per-rank kernel and
 all-reduce times) runs on the one-GPU test box (tests/test_bench_multirank_gpu.py), labelled "not a scaling measurement".
 
-One JSON line is printed by rank 0.  Extra objects:
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the --steps steps, writes the last step's
+product if --dump-outputs is given and prints the line; its extra object:
   roofline     : dense-equivalent algorithmic bytes B_alg = 4N^2 + 4N(d+2T) / mean duration of the
                  dominant kernel (mvm_tile_kernel), measured with HIP events on the launch stream (rpgp_profile_*).
-  cpu_baseline : oracle/cpu_path.py (torch-CPU restatement of the reference's op sequence) on a bounded row sample of
-                 the same MVM, on rank 0 at N=1 only.
+`--full` adds everything beside the headline:
+  prepare_us   : the per-hyper-parameter-step projection + prepare, and the step time with it amortised (N=1 only).
+  extras       : T=11 block, solves, cached-K / packed-cache / SKI modes, derivative, optimiser steps (N=1 only;
+                 --no-extras skips them).
+  cpu_baseline : oracle/cpu_path.py (torch-CPU restatement of the reference's op sequence) and oracle/cmvm.c on bounded
+                 row samples of the same MVM, on rank 0 at N=1 only (--cpu-budget 0 skips them).
+  multi_gpu.other_split : with --gpus N > 1, the split --shard does not name, timed in the same run (--one-split skips it).
+
+`--dump-outputs DIR` writes the product of the last timed step (what a caller of the timed path receives) as
+DIR/mvm_out.npy (float32, N x T); above 64 MB a fixed, seeded sample of rows is written instead, with the row indices in
+DIR/mvm_out_rows.npy (float64).  The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -50,10 +60,17 @@ def main():
     ap.add_argument("--J", type=int, default=20)
     ap.add_argument("--T", type=int, default=1)
     ap.add_argument("--shard", choices=["pairs", "j"], default="pairs", help="multi-GPU split of the MVM")
-    ap.add_argument("--one-split", action="store_true", help="with --gpus N > 1 time only the split --shard names (default: both)")
+    ap.add_argument("--one-split", action="store_true",
+                    help="with --full and --gpus N > 1 time only the split --shard names (default there: both)")
     ap.add_argument("--direct", action="store_true", help="use the exact direct kernel instead of the factorised path")
-    ap.add_argument("--no-extras", action="store_true", help="skip the T=11 block / full-solve context numbers")
-    ap.add_argument("--cpu-budget", type=float, default=15.0, help="seconds of CPU work for cpu_baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is beside the headline: prepare time, extras (T=11 block, solves, other modes, "
+                         "optimiser steps), CPU baselines, and with --gpus N > 1 the other split")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the product of the last timed step as DIR/mvm_out.npy (float32; a seeded row sample "
+                         "above 64 MB)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the T=11 block / full-solve context numbers")
+    ap.add_argument("--cpu-budget", type=float, default=15.0, help="with --full: seconds of CPU work for cpu_baseline (0 = skip)")
     ap.add_argument("--comm", choices=["rccl", "ipc"], default=None,
                     help="all-reduce of the sharded step: rccl (torch.distributed 'nccl' = RCCL over xGMI; default on a "
                          "multi-GPU node) or ipc (rpgp_comm: one-shot kernel over IPC-mapped peer buffers; the default — and "
@@ -71,6 +88,8 @@ def main():
     #  parser abbreviation-matches flags such as --n against its own --nnodes / --nproc-per-node before it reaches the script)
     argv = json.loads(os.environ["RPGP_BENCH_ARGV"]) if ("RPGP_BENCH_ARGV" in os.environ and len(sys.argv) == 1) else None
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU) through
@@ -140,7 +159,7 @@ def main():
     # tables of the factorised form (range pass, midpoints, row / column records, the status word read back) — wall time per
     # call between synchronisations, mean of 20 after one warm call
     prepare_us = None
-    if prep is not None and world == 1:
+    if args.full and prep is not None and world == 1:
         ops.Prepared(ops.project(X, Peff))
         torch.cuda.synchronize()
         tp = time.perf_counter()
@@ -244,7 +263,7 @@ def main():
 
     primary = run_split(args.shard if world > 1 else "single")
     other = None
-    if world > 1 and not args.one_split:
+    if args.full and world > 1 and not args.one_split:
         other = run_split("j" if args.shard == "pairs" else "pairs")
     elapsed, kernel_ms, per_rank, res = primary["elapsed"], primary["kernel_ms"], primary["per_rank"], primary["res"]
     if args.dump_result and rank == 0:
@@ -252,6 +271,8 @@ def main():
         np.save(args.dump_result, res.detach().cpu().numpy())
         if other is not None:
             np.save(args.dump_result + ".other.npy", other["res"].detach().cpu().numpy())
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, res)
 
     ms_per_step = elapsed / args.steps * 1e3
     value = args.steps / elapsed
@@ -353,7 +374,7 @@ def main():
                                            "it); this run proves the N>1 code path end to end, nothing about speed-up" % world)
             result["scaling"] = "strong"
 
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         # context numbers (not part of `value`): the T=11 block the training solve uses (10 probes + residual), and one
         # full solve Khat^-1 y with the reference's eval tolerance (SURVEY.md §8(d) "unit of work")
         from rpgp_amd import settings, linear_cg as lcg
@@ -532,7 +553,7 @@ def main():
             "ms_per_step": round(ms_per_step + prepare_us * 1e-3 / max(its or 1, 1), 4),
             "mvm_per_s": round(1e3 / (ms_per_step + prepare_us * 1e-3 / max(its or 1, 1)), 3)}
 
-    if rank == 0 and world == 1 and args.cpu_budget > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0:
         from oracle import cpu_path
         torch.set_num_threads(os.cpu_count() or 1)
         Zc, Vc = Z.cpu(), V.cpu()
@@ -573,6 +594,23 @@ def main():
         if reducer is not None:
             reducer.close()
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_outputs(out_dir, res):
+    """DIR/mvm_out.npy: the (all-reduced) N x T product of the last timed step as float32.  Above DUMP_LIMIT_BYTES a fixed
+    sample of rows (seed 0, sorted) is written instead, and its row indices as DIR/mvm_out_rows.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = res.detach().float().cpu().numpy()
+    if out.nbytes > DUMP_LIMIT_BYTES:
+        n_rows = DUMP_LIMIT_BYTES // (out.itemsize * out.shape[1] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(out.shape[0], size=n_rows, replace=False))
+        np.save(os.path.join(out_dir, "mvm_out_rows.npy"), rows.astype(np.float64))
+        out = out[rows]
+    np.save(os.path.join(out_dir, "mvm_out.npy"), np.ascontiguousarray(out))
 
 
 def _step_times(device):

@@ -29,14 +29,21 @@ def _oracle_rows(N, rows):
     return cmvm.mvm(Z[rows], Z, Vh, 1.0 / J) + 0.1 * Vh[rows]
 
 
-# (world, split that is `value`, N): every run times BOTH splits (the other one lands in multi_gpu.other_split), so the
-# last case is north_star's uneven J = 20 -> (3,3,3,3,2,2,2,2) split AND the equal-pairs split at world 8 on the BASELINE
-# size N = 50 000 (VERDICT r5 #1b)
-@pytest.mark.parametrize("world,shard,N", [(2, "pairs", 20000), (3, "j", 20000), (8, "pairs", 50000)])
+# (world, split that is `value`, N): every --full run times BOTH splits (the other one lands in multi_gpu.other_split), so
+# the last case is north_star's uneven J = 20 -> (3,3,3,3,2,2,2,2) split AND the equal-pairs split at world 8 on the BASELINE
+# size N = 50 000 (VERDICT r5 #1b).  Eight ranks sharing one device exceed the number of processes a GPU test may keep on
+# a device at once, so that case runs one rank per GPU and needs 8 of them; the 4-rank case keeps the BASELINE size on one
+# device.
+@pytest.mark.parametrize("world,shard,N", [(2, "pairs", 20000), (3, "j", 20000), (4, "pairs", 50000), (8, "pairs", 50000)])
 def test_bench_gpus_n_runs_on_one_device(gpu_device, tmp_path, world, shard, N):
+    import torch
+    shared = world < 8
+    if not shared and torch.cuda.device_count() < world:
+        pytest.skip("needs %d GPUs (one rank each), found %d" % (world, torch.cuda.device_count()))
     dump = str(tmp_path / "res.npy")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--all-ranks-on-device", "0", "--shard", shard,
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--shard", shard, "--full",
            "--n", str(N), "--steps", "5", "--warmup", "2", "--no-extras", "--cpu-budget", "0", "--dump-result", dump]
+    cmd += ["--all-ranks-on-device", "0"] if shared else ["--comm", "ipc"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
@@ -56,7 +63,10 @@ def test_bench_gpus_n_runs_on_one_device(gpu_device, tmp_path, world, shard, N):
     mg = res["multi_gpu"]
     assert len(mg["per_rank_kernel_ms"]) == world and all(k > 0 for k in mg["per_rank_kernel_ms"])
     assert len(mg["per_rank_allreduce_us"]) == world and mg["allreduce_us"] > 0 and mg["allreduce_bytes"] == 4 * N
-    assert mg["all_ranks_on_device"] == 0 and "NOT a scaling measurement" in mg["note"]
+    if shared:
+        assert mg["all_ranks_on_device"] == 0 and "NOT a scaling measurement" in mg["note"]
+    else:
+        assert "all_ranks_on_device" not in mg
     assert abs(res["roofline"]["kernel_ms"] - max(mg["per_rank_kernel_ms"])) < 1e-3
     assert res["roofline"]["traffic"] is None and "cpu_baseline" not in res
     # the kernel the line names is the one the split launches (the hand-scheduled kernel serves the pair shares)
@@ -72,3 +82,27 @@ def test_bench_gpus_n_runs_on_one_device(gpu_device, tmp_path, world, shard, N):
         out = np.load(path).astype(np.float64)
         assert out.shape == (N, 1)
         assert np.linalg.norm(out[rows] - ref) / np.linalg.norm(ref) < 1e-5, path
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_product(gpu_device, tmp_path):
+    """A plain `bench.py --gpus 1` run: the headline line only (nothing that `--full` adds), exactly --steps timed steps, and
+    `--dump-outputs` writes the product of the last timed step, checked against the float64 oracle on a seeded row sample."""
+    N = 20000
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--n", str(N), "--steps", "7", "--warmup", "1",
+           "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["n_gpus"] == 1 and res["steps"] == 7 and res["warmup"] == 1 and res["unit"] == "MVM/s"
+    assert res["higher_is_better"] is True and res["dtype"] == "f32" and res["metric"].startswith("additive-RP kernel MVMs/sec")
+    assert res["value"] > 0 and abs(res["value"] * res["ms_per_step"] / 1e3 - 1.0) < 1e-3
+    assert not {"extras", "cpu_baseline", "cpu_baseline_best", "prepare_us", "multi_gpu"} & set(res)
+    assert sorted(os.listdir(out_dir)) == ["mvm_out.npy"]
+    out = np.load(out_dir / "mvm_out.npy")
+    assert out.dtype == np.float32 and out.shape == (N, 1)
+    rows = np.sort(np.random.default_rng(1).choice(N, size=384, replace=False))
+    ref = _oracle_rows(N, rows)
+    assert np.linalg.norm(out[rows].astype(np.float64) - ref) / np.linalg.norm(ref) < 1e-5

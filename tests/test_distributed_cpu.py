@@ -221,6 +221,28 @@ def test_bench_gpus_flag_starts_ranks():
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample_above_the_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs DIR`: the last step's product as DIR/mvm_out.npy in float32; above the size limit a fixed,
+    seeded row sample with its row indices (float64), the same rows in every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    res = torch.arange(24, dtype=torch.float32).reshape(12, 2)
+    bench._dump_outputs(str(tmp_path / "all"), res)
+    assert sorted(os.listdir(tmp_path / "all")) == ["mvm_out.npy"]
+    out = np.load(tmp_path / "all" / "mvm_out.npy")
+    assert out.dtype == np.float32 and np.array_equal(out, res.numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 64)               # 64 // (2 * 4 + 8) = 4 rows
+    picked = []
+    for name in ("s1", "s2"):
+        bench._dump_outputs(str(tmp_path / name), res.double())
+        rows = np.load(tmp_path / name / "mvm_out_rows.npy")
+        out = np.load(tmp_path / name / "mvm_out.npy")
+        assert rows.dtype == np.float64 and out.dtype == np.float32 and out.shape == (4, 2)
+        assert np.array_equal(out, res.numpy()[rows.astype(np.int64)])
+        picked.append(rows)
+    assert np.array_equal(picked[0], picked[1]) and np.all(np.diff(picked[0]) > 0)
+
+
 def _row_sharded_ski_worker(rank, world, port, tmpdir):
     sys.path.insert(0, ROOT)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
