@@ -115,6 +115,34 @@ int rpgp_mvm_sym_prepared_range(const void *prep, const float *V, float *out, in
                                 void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Chebyshev low-rank form of the prepared symmetric MVM.  On the centred coordinates of rpgp_prepare every 1-D term is
+ * exp2(-h^2 (x - y)^2) with x = a'/h, y = b'/h in [-1, 1] (h = max_abs of rpgp_prepare_status), which is numerically low-rank:
+ * K_j ~ T(x_j) C T(x_j)^T with the p x p Chebyshev coefficients C of that function.  The product then costs ~4 N J p FMAs
+ * and no exponentials.  p is the smallest rank whose discarded coefficient tail sum_{max(m,n) >= p} |c_mn| (a bound on the
+ * error of every kernel entry, since |T_m| <= 1) is <= 2^-26; results differ from the sweep at the 1e-7 level, not only in
+ * summation order.
+ *   rpgp_lowrank_select (host only, no device): the rank for a half-width h, 0 when it exceeds p_max (<= 128) or the reference
+ *     degree 128 does not resolve the function; `tail_host` (optional) receives the claimed bound, `coef_host` (optional,
+ *     p_max x p_max row-major) the p x p float64 coefficients.
+ *   rpgp_lowrank_create: plan of one prepared buffer (call after rpgp_prepare, once per Z) in the caller's device buffer of
+ *     rpgp_lowrank_plan_bytes; *p_host = 0 and *handle_host = NULL when the range needs more than 64 (not served: use
+ *     rpgp_mvm_sym_prepared_range).  Synchronises the stream.  The handle is host memory: rpgp_lowrank_destroy frees it (the
+ *     device buffer stays the caller's).
+ *   rpgp_mvm_sym_lowrank_range: same arguments and result contract as rpgp_mvm_sym_prepared_range plus the handle; a rank of
+ *     (world, rank) writes its row slice [N r / world, N (r + 1) / world) of scale * K v and noise * V on every row; repeated
+ *     calls are bit-identical.  Workspace: rpgp_mvm_sym_lowrank_workspace_bytes.
+ */
+int rpgp_lowrank_select(double h, int p_max, int *p_host, double *tail_host, double *coef_host);
+size_t rpgp_lowrank_plan_bytes(int64_t N, int J);
+int rpgp_lowrank_create(const void *prep, int64_t N, int J, float max_abs, void *plan, size_t plan_bytes, int *p_host,
+                        void **handle_host, void *stream);
+int rpgp_lowrank_destroy(void *handle);
+size_t rpgp_mvm_sym_lowrank_workspace_bytes(const void *handle, int64_t N, int T);
+int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float *V, float *out, int64_t N, int J, int T,
+                               int j0, int j1, int world, int rank, float scale, float noise,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Rectangular fused MVM:  out = scale * sum_j K_j(Z1,Z2) @ V      (Z1: M x ., Z2: N x ., V: N x T, out: M x T)
  * Replaces K(X*,X) @ alpha and K(X,X*) blocks of the prediction strategy driven from training_routines.py:551-575.
  */

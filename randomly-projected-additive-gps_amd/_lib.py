@@ -41,6 +41,13 @@ SIGNATURES = {
     "rpgp_mvm_sym_range": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _f32, _f32, _vp, _sz, _vp]),
     "rpgp_mvm_sym_prepared_range": (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _f32, _f32, _vp, _sz,
                                            _vp]),
+    "rpgp_lowrank_select": (_int, [_f64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), _vp]),
+    "rpgp_lowrank_plan_bytes": (_sz, [_i64, _int]),
+    "rpgp_lowrank_create": (_int, [_vp, _i64, _int, _f32, _vp, _sz, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_vp), _vp]),
+    "rpgp_lowrank_destroy": (_int, [_vp]),
+    "rpgp_mvm_sym_lowrank_workspace_bytes": (_sz, [_vp, _i64, _int]),
+    "rpgp_mvm_sym_lowrank_range": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _int, _f32, _f32, _vp, _sz,
+                                          _vp]),
     "rpgp_mvm_rect_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "rpgp_mvm_rect": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
     "rpgp_dense": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _int, _int, _f32, _vp]),

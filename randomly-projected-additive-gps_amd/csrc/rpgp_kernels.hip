@@ -3597,6 +3597,16 @@ int sum_columns_launch(const float *x, float *out, int n, int C, float mul, hipS
   hipLaunchKernelGGL(sum_columns_kernel, dim3(C), dim3(1024), 0, st, x, out, n, C, mul);
   return (int)hipGetLastError();
 }
+// the rpgp_profile_* hook for products launched from other translation units (rpgp_lowrank.hip)
+bool prof_open(hipStream_t st) {
+  if (!g_prof_on || g_prof_n >= kProfMax) return false;
+  return hipEventRecord(g_prof_ev[2 * g_prof_n], st) == hipSuccess;
+}
+int prof_close(hipStream_t st) {
+  RPGP_CHECK(hipEventRecord(g_prof_ev[2 * g_prof_n + 1], st));
+  ++g_prof_n;
+  return 0;
+}
 }  // namespace rpgp_internal
 
 extern "C" {

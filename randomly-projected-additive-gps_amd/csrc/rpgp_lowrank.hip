@@ -1,0 +1,390 @@
+// rpgp_lowrank.hip — Chebyshev low-rank form of the prepared symmetric MVM (gfx950).
+//
+// On the centred, exp2-scaled coordinates of rpgp_prepare every 1-D term is exp2(-(a - b)^2) with |a|, |b| <= h
+// (h = max_abs of the prep header).  With x = a / h on [-1, 1]:
+//   exp2(-h^2 (x - y)^2) = sum_{m,n < p} c_mn T_m(x) T_n(y) + tail,   |tail| <= sum_{max(m,n) >= p} |c_mn|  (|T_m| <= 1)
+// so   K_j v = T(x_j) (C (T(x_j)^T v))   costs ~4 N p FMAs per projection and no transcendentals.  The rank p is chosen on
+// the host (double precision) so that the discarded tail is <= 2^-26 per kernel entry, below fp32 rounding of the entries.
+//
+// Plan (once per Z, after rpgp_prepare): the p x p coefficients in fp32 (zero-padded to PB = p rounded up to 8) and the
+// coordinates x = a / h transposed to [J][N] (one coalesced row per projection), both in a caller-owned device buffer.
+// Product: three launches, no float atomics (repeated calls are bit-identical):
+//   (a) project  W_j[n][t]  = sum_i T_n(x_ij) v_it           per (row block, projection, t): block partials
+//   (b) combine  U_j[m][t]  = scale * sum_n c_mn W_j[n][t]   per (projection, t): partials summed in a fixed order
+//   (c) output   out_it     = sum_j sum_m T_m(x_ij) U_j[m][t] (Clenshaw) + noise * v_it
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <new>
+#include <vector>
+
+#include "../../include/rpgp.h"
+#include "rpgp_internal.h"
+
+namespace {
+
+typedef float float2v __attribute__((ext_vector_type(2)));
+
+// rpgp_prepare's buffer (rpgp_kernels.hip): [header 64 floats][mid 64 floats][rowdat N*J float2 {a, exp2(-a^2)}][...]
+constexpr int kPrepRowdatOffsetFloats = 128;
+constexpr int kPrepMaxJ = 64;
+
+constexpr int kRefDegree = 128;          // reference degree of the 2-D Chebyshev interpolant (rank selection)
+constexpr int kMaxRank = 64;             // largest rank a plan serves (PB <= 64 floats of accumulators per lane)
+constexpr double kTailTol = 1.0 / (1 << 26);
+constexpr int kProjRowsPerThread = 8;    // pass (a): 2 048 rows per workgroup
+constexpr int kProjRows = 256 * kProjRowsPerThread;
+constexpr int kOutRows = 64;             // pass (c): 64 rows x 4 projection groups per workgroup
+
+struct LowrankPlan {
+  int p, pb;                             // rank and padded rank (multiple of 8)
+  int64_t N;
+  int J;
+  double h, tail;
+  const float *coef;                     // pb x pb, fp32, zero outside p x p
+  const float *xt;                       // J x N coordinates x = a / h
+};
+
+inline int pad8(int p) { return (p + 7) & ~7; }
+inline int proj_blocks(int64_t N) { return (int)((N + kProjRows - 1) / kProjRows); }
+
+// ---- rank selection (host, double) ------------------------------------------------------------------------------
+// coefficients of the degree-(M-1) interpolant of f(x, y) = exp2(-h^2 (x - y)^2) at the M x M Chebyshev points of the
+// first kind (a separable DCT-II), c[m * M + n]
+void cheb2d_coefficients(double h, std::vector<double> &c) {
+  const int M = kRefDegree;
+  std::vector<double> xs(M), cs((size_t)M * M), f((size_t)M * M), g((size_t)M * M);
+  for (int k = 0; k < M; ++k) xs[k] = cos(M_PI * (k + 0.5) / M);
+  for (int m = 0; m < M; ++m)
+    for (int k = 0; k < M; ++k) cs[(size_t)m * M + k] = cos(M_PI * m * (k + 0.5) / M);
+  const double h2 = h * h;
+  for (int k = 0; k < M; ++k)
+    for (int l = 0; l <= k; ++l) {
+      const double d = xs[k] - xs[l];
+      f[(size_t)k * M + l] = f[(size_t)l * M + k] = exp2(-h2 * d * d);
+    }
+  // g[k][n] = sum_l f[k][l] cos_n(l);  c[m][n] = sum_k cos_m(k) g[k][n]
+  for (int k = 0; k < M; ++k)
+    for (int n = 0; n < M; ++n) {
+      double s = 0.0;
+      for (int l = 0; l < M; ++l) s += f[(size_t)k * M + l] * cs[(size_t)n * M + l];
+      g[(size_t)k * M + n] = s;
+    }
+  c.assign((size_t)M * M, 0.0);
+  for (int m = 0; m < M; ++m) {
+    for (int k = 0; k < M; ++k) {
+      const double w = cs[(size_t)m * M + k];
+      for (int n = 0; n < M; ++n) c[(size_t)m * M + n] += w * g[(size_t)k * M + n];
+    }
+    const double wm = (m == 0 ? 1.0 : 2.0) / M;
+    for (int n = 0; n < M; ++n) c[(size_t)m * M + n] *= wm * (n == 0 ? 1.0 : 2.0) / M;
+  }
+}
+
+// smallest p with sum_{max(m,n) >= p} |c_mn| <= tol; 0 when the reference degree does not resolve f or p > p_max.
+// `tail` receives the bound of the chosen p (plus a rounding allowance of the fp64 transform).
+int select_rank(double h, int p_max, double tol, double *tail, std::vector<double> &c) {
+  const int M = kRefDegree;
+  if (!(h >= 0.0) || !isfinite(h)) return 0;
+  cheb2d_coefficients(h, c);
+  // shell sums: s[q] = sum_{max(m,n) == q} |c_mn|
+  std::vector<double> shell(M, 0.0);
+  for (int m = 0; m < M; ++m)
+    for (int n = 0; n < M; ++n) shell[m > n ? m : n] += fabs(c[(size_t)m * M + n]);
+  double unresolved = 0.0;                 // the last 8 shells: must be at the rounding level of the transform
+  for (int q = M - 8; q < M; ++q) unresolved += shell[q];
+  if (unresolved > 1e-11) return 0;
+  const double allowance = 1e-13 + unresolved;
+  double t = 0.0;
+  int p = M;
+  for (int q = M - 1; q >= 1; --q) {       // tail of p = q is the sum of the shells q .. M-1
+    if (t + shell[q] + allowance > tol) break;
+    t += shell[q];
+    p = q;
+  }
+  if (p > p_max) return 0;
+  if (tail) *tail = t + allowance;
+  return p;
+}
+
+// ---- device -----------------------------------------------------------------------------------------------------
+// one DPP move of a float64 (two 32-bit halves)
+template <int CTRL> __device__ __forceinline__ double dpp_d(double v) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_mov_dpp((int)b, CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_mov_dpp((int)(b >> 32), CTRL, 0xf, 0xf, false);
+  return __builtin_bit_cast(double, (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+__device__ __forceinline__ double readlane_d(double v, int lane) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = __builtin_amdgcn_readlane((int)b, lane), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
+  return __builtin_bit_cast(double, (long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+}
+// sum over the 64 lanes of a wave, the same value in every lane: quad / half-row / row by DPP, then the four rows
+__device__ __forceinline__ double wave_sum(double v) {
+  v += dpp_d<0xb1>(v);    // quad_perm [1,0,3,2]
+  v += dpp_d<0x4e>(v);    // quad_perm [2,3,0,1]
+  v += dpp_d<0x141>(v);   // row_half_mirror
+  v += dpp_d<0x140>(v);   // row_mirror
+  return (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + readlane_d(v, 48));
+}
+
+// plan: xt[j][n] = a_nj * inv_h
+__global__ __launch_bounds__(256) void lr_coords_kernel(const float2v *__restrict__ rowdat, float *__restrict__ xt,
+                                                        long long N, int J, float inv_h) {
+  const long long total = N * J;
+  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
+    const int j = (int)(g / N);
+    const long long n = g - (long long)j * N;
+    xt[g] = rowdat[n * J + j].x * inv_h;
+  }
+}
+
+// (a) block partials part[b][jj][t][0..PB) = sum over the block's rows of T_m(x_ij) v_it.  grid (row blocks, jn, T)
+// The sums are float64 (T_m v exact, then added): W is a sum of N terms of both signs that C turns into a much smaller
+// product — in float32 its rounding alone is ~1e-6 of the result (measured in an emulation at N = 20 011), in float64 ~3e-8.
+template <int PB>
+__global__ __launch_bounds__(256) void lr_project_kernel(const float *__restrict__ xt, const float *__restrict__ V,
+                                                         double *__restrict__ part, int N, int T, int j0, int jn) {
+  __shared__ double red[4][PB];
+  const int b = blockIdx.x, jj = blockIdx.y, t = blockIdx.z;
+  const float *x = xt + (size_t)(j0 + jj) * N;
+  const int r0 = b * kProjRows + (int)threadIdx.x;
+  float xv[kProjRowsPerThread], vv[kProjRowsPerThread];
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {          // every load requested before the first use
+    const int i = r0 + u * 256;
+    const bool ok = i < N;
+    xv[u] = ok ? x[i] : 0.f;
+    vv[u] = ok ? V[(size_t)i * T + t] : 0.f;
+  }
+  double acc[PB];
+#pragma unroll
+  for (int m = 0; m < PB; ++m) acc[m] = 0.0;
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {
+    const float xi = xv[u], v = vv[u], x2 = 2.f * xi;
+    float tm2 = 1.f, tm1 = xi;
+    acc[0] += (double)v;
+    acc[1] = __builtin_fma((double)xi, (double)v, acc[1]);
+#pragma unroll
+    for (int m = 2; m < PB; ++m) {
+      const float tm = __builtin_fmaf(x2, tm1, -tm2);     // T_m = 2x T_{m-1} - T_{m-2}
+      acc[m] = __builtin_fma((double)tm, (double)v, acc[m]);
+      tm2 = tm1;
+      tm1 = tm;
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 0; m < PB; ++m) {
+    const double s = wave_sum(acc[m]);
+    if (lane == 0) red[w][m] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    const int m = threadIdx.x;
+    part[(((size_t)b * jn + jj) * T + t) * PB + m] = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
+  }
+}
+
+// (b) U[jj][t][m] = scale * sum_n c_mn W[n],  W[n] = sum_b part[b][jj][t][n] (b in a fixed order; float64, U rounded to
+// float32 at the end).  grid (jn, T)
+template <int PB>
+__global__ __launch_bounds__(256) void lr_combine_kernel(const double *__restrict__ part, const float *__restrict__ coef,
+                                                         float *__restrict__ U, int nblk, int T, int jn, float scale) {
+  constexpr int G = 256 / PB;
+  __shared__ double sw[G][PB];
+  __shared__ double w[PB];
+  const int jj = blockIdx.x, t = blockIdx.y;
+  const int n = threadIdx.x % PB, g = threadIdx.x / PB;
+  if (g < G) {
+    double s = 0.0;
+    for (int b = g; b < nblk; b += G) s += part[(((size_t)b * jn + jj) * T + t) * PB + n];
+    sw[g][n] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    double s = sw[0][threadIdx.x];
+#pragma unroll
+    for (int q = 1; q < G; ++q) s += sw[q][threadIdx.x];
+    w[threadIdx.x] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    const int m = threadIdx.x;
+    double s = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < PB; ++k) s = __builtin_fma((double)coef[m * PB + k], w[k], s);
+    U[((size_t)jj * T + t) * PB + m] = (float)((double)scale * s);
+  }
+}
+
+// (c) out_it = sum_j sum_m T_m(x_ij) U[j][t][m] + noise v_it on this rank's rows [r0, r1); noise v_it (or 0) elsewhere.
+// A workgroup: 64 rows x 4 groups of projections (group g takes jj = g, g + 4, ...), the groups' sums added in order.
+// grid (row blocks of 64, T)
+template <int PB>
+__global__ __launch_bounds__(256) void lr_output_kernel(const float *__restrict__ xt, const float *__restrict__ U,
+                                                        const float *__restrict__ V, float *__restrict__ out, int N, int T,
+                                                        int j0, int jn, int r0, int r1, float noise) {
+  __shared__ float su[kPrepMaxJ * PB];
+  __shared__ float sacc[4][kOutRows];
+  const int t = blockIdx.y;
+  for (int e = threadIdx.x; e < jn * PB; e += 256) su[e] = U[((size_t)(e / PB) * T + t) * PB + e % PB];
+  __syncthreads();
+  const int r = threadIdx.x & (kOutRows - 1), g = threadIdx.x / kOutRows;
+  const int i = blockIdx.x * kOutRows + r;
+  const bool mine = i >= r0 && i < r1;
+  constexpr int kMaxPer = kPrepMaxJ / 4;
+  float xv[kMaxPer];
+#pragma unroll
+  for (int q = 0; q < kMaxPer; ++q) {                     // this lane's coordinates, requested together
+    const int jj = g + 4 * q;
+    xv[q] = (mine && jj < jn) ? xt[(size_t)(j0 + jj) * N + i] : 0.f;
+  }
+  float acc = 0.f;
+#pragma unroll
+  for (int q = 0; q < kMaxPer; ++q) {
+    const int jj = g + 4 * q;
+    if (jj >= jn) break;
+    const float *u = su + jj * PB;
+    const float x = xv[q], x2 = 2.f * x;
+    float b1 = 0.f, b2 = 0.f;                             // Clenshaw: b_k = U_k + 2x b_{k+1} - b_{k+2}
+#pragma unroll
+    for (int k = PB - 1; k >= 1; --k) {
+      const float bk = __builtin_fmaf(x2, b1, u[k] - b2);
+      b2 = b1;
+      b1 = bk;
+    }
+    acc += __builtin_fmaf(x, b1, u[0] - b2);
+  }
+  sacc[g][r] = acc;
+  __syncthreads();
+  if (g != 0 || i >= N) return;
+  const size_t o = (size_t)i * T + t;
+  float res = mine ? (sacc[0][r] + sacc[1][r]) + (sacc[2][r] + sacc[3][r]) : 0.f;
+  if (noise != 0.f) res = __builtin_fmaf(noise, V[o], res);
+  out[o] = res;
+}
+
+template <int PB>
+int launch_lowrank(const LowrankPlan &P, const float *V, float *out, int N, int T, int j0, int jn, int r0, int r1,
+                   float scale, float noise, double *part, float *U, hipStream_t st) {
+  const int nblk = proj_blocks(N);
+  hipLaunchKernelGGL(lr_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, V, part, N, T, j0, jn);
+  hipLaunchKernelGGL(lr_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, U, nblk, T, jn, scale);
+  hipLaunchKernelGGL(lr_output_kernel<PB>, dim3((N + kOutRows - 1) / kOutRows, T), dim3(256), 0, st, P.xt, U, V, out, N, T,
+                     j0, jn, r0, r1, noise);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" {
+
+int rpgp_lowrank_select(double h, int p_max, int *p_host, double *tail_host, double *coef_host) {
+  if (!p_host || p_max < 1 || p_max > kRefDegree) return RPGP_EINVAL;
+  std::vector<double> c;
+  double tail = 0.0;
+  const int p = select_rank(h, p_max, kTailTol, &tail, c);
+  *p_host = p;
+  if (tail_host) *tail_host = p ? tail : 0.0;
+  if (coef_host && p)
+    for (int m = 0; m < p; ++m)
+      for (int n = 0; n < p; ++n) coef_host[(size_t)m * p_max + n] = c[(size_t)m * kRefDegree + n];
+  return 0;
+}
+
+size_t rpgp_lowrank_plan_bytes(int64_t N, int J) {
+  if (N <= 0 || J <= 0 || J > kPrepMaxJ) return 0;
+  return ((size_t)kMaxRank * kMaxRank + (size_t)N * J) * sizeof(float);
+}
+
+int rpgp_lowrank_create(const void *prep, int64_t N, int J, float max_abs, void *plan, size_t plan_bytes, int *p_host,
+                        void **handle_host, void *stream) {
+  if (!prep || !plan || !p_host || !handle_host || N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ)
+    return RPGP_EINVAL;
+  if (plan_bytes < rpgp_lowrank_plan_bytes(N, J)) return RPGP_EWORKSPACE;
+  *p_host = 0;
+  *handle_host = nullptr;
+  // a slightly wider interval than max|a| absorbs the rounding of a = (z - mid) * c at the ends of the range
+  const double h = (double)max_abs * (1.0 + 1.0 / (1 << 20));
+  std::vector<double> c;
+  double tail = 0.0;
+  const int p = select_rank(h, kMaxRank, kTailTol, &tail, c);
+  if (p == 0) return 0;                                   // not served: the sweep runs
+  const int pb = pad8(p);
+  std::vector<float> cf((size_t)pb * pb, 0.f);
+  for (int m = 0; m < p; ++m)
+    for (int n = 0; n < p; ++n) cf[(size_t)m * pb + n] = (float)c[(size_t)m * kRefDegree + n];
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float *coef = reinterpret_cast<float *>(plan);
+  float *xt = coef + (size_t)kMaxRank * kMaxRank;
+  hipError_t e = hipMemcpyAsync(coef, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return (int)e;
+  // (rank 1: T_0 = 1 whatever x is; h = 0 would divide by zero)
+  const float inv_h = (p == 1 || !(h > 0.0)) ? 0.f : (float)(1.0 / h);
+  const long long total = N * J;
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  const float2v *rowdat = reinterpret_cast<const float2v *>(reinterpret_cast<const float *>(prep) + kPrepRowdatOffsetFloats);
+  hipLaunchKernelGGL(lr_coords_kernel, dim3(blocks), dim3(256), 0, st, rowdat, xt, (long long)N, J, inv_h);
+  int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  e = hipStreamSynchronize(st);                           // (the host copy of the coefficients goes out of scope)
+  if (e != hipSuccess) return (int)e;
+  LowrankPlan *P = new (std::nothrow) LowrankPlan{p, pb, N, J, h, tail, coef, xt};
+  if (!P) return RPGP_EINVAL;
+  *p_host = p;
+  *handle_host = P;
+  return 0;
+}
+
+int rpgp_lowrank_destroy(void *handle) {
+  delete reinterpret_cast<LowrankPlan *>(handle);
+  return 0;
+}
+
+size_t rpgp_mvm_sym_lowrank_workspace_bytes(const void *handle, int64_t N, int T) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P || N <= 0 || N > 0x7fffffffLL || T <= 0) return 0;
+  return (size_t)P->J * T * P->pb * ((size_t)proj_blocks(N) * sizeof(double) + sizeof(float));
+}
+
+int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float *V, float *out, int64_t N, int J, int T,
+                               int j0, int j1, int world, int rank, float scale, float noise, void *workspace,
+                               size_t workspace_bytes, void *stream) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P || !prep || !V || !out || N <= 0 || T <= 0 || J <= 0 || J > kPrepMaxJ || j0 < 0 || j1 <= j0 || j1 > J)
+    return RPGP_EINVAL;
+  if (N != P->N || J != P->J || T > 65535) return RPGP_EINVAL;
+  if (world < 1 || rank < 0 || rank >= world) return RPGP_EINVAL;
+  const size_t need = rpgp_mvm_sym_lowrank_workspace_bytes(handle, N, T);
+  if (!workspace || workspace_bytes < need) return RPGP_EWORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int n = (int)N, jn = j1 - j0;
+  // a rank of a pair-sharded call writes its row slice of K v (and the noise term, if it was given one, on every row)
+  const int r0 = (int)((int64_t)n * rank / world), r1 = (int)((int64_t)n * (rank + 1) / world);
+  double *part = reinterpret_cast<double *>(workspace);
+  float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
+  const bool prof = rpgp_internal::prof_open(st);
+  int rc;
+  switch (P->pb) {
+    case 8: rc = launch_lowrank<8>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 16: rc = launch_lowrank<16>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 24: rc = launch_lowrank<24>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 32: rc = launch_lowrank<32>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 40: rc = launch_lowrank<40>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 48: rc = launch_lowrank<48>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 56: rc = launch_lowrank<56>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    case 64: rc = launch_lowrank<64>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
+    default: return RPGP_EINVAL;
+  }
+  if (prof) {
+    const int pc = rpgp_internal::prof_close(st);
+    if (!rc) rc = pc;
+  }
+  return rc;
+}
+
+}  // extern "C"

@@ -2,6 +2,8 @@
 
 All functions require CUDA(=HIP) float32 contiguous tensors and launch on the caller's current stream.
 """
+import os
+
 import torch
 
 from . import _lib
@@ -203,6 +205,9 @@ class Prepared:
         self.fast_ok = False
         self.max_abs = float("inf")
         self.buf = None
+        self._rank = None              # Chebyshev low-rank plan (rpgp_lowrank_create): built on the first product
+        self._plan = None
+        self._handle = None
         if self.J > 64:
             return
         with _on(Z.device):
@@ -216,9 +221,43 @@ class Prepared:
         self.fast_ok = bool(ok.value)
         self.max_abs = float(mx.value)
 
+    @property
+    def rank(self):
+        """Rank p of the low-rank plan of this Z (0: not served — the range needs more than 64 — or not fast_ok).  The plan is
+        built on first use, so that a Prepared that only feeds the native solver (which runs the sweep) does not pay for it."""
+        if self._rank is None:
+            import ctypes
+            self._rank = 0
+            if self.fast_ok:
+                lib = _lib.load()
+                with _on(self.device):
+                    self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes(self.N, self.J)), dtype=torch.uint8,
+                                             device=self.device)
+                    p, h = ctypes.c_int(0), ctypes.c_void_p(None)
+                    _lib.check(lib.rpgp_lowrank_create(self.buf.data_ptr(), self.N, self.J, self.max_abs,
+                                                       self._plan.data_ptr(), self._plan.numel(), ctypes.byref(p),
+                                                       ctypes.byref(h), _stream()), "rpgp_lowrank_create")
+                self._rank, self._handle = int(p.value), h.value
+                if not self._rank:
+                    self._plan = None
+        return self._rank
+
+    def __del__(self):
+        if getattr(self, "_handle", None):
+            _lib.load().rpgp_lowrank_destroy(self._handle)
+            self._handle = None
+
+
+def lowrank_enabled():
+    """The prepared product takes the Chebyshev low-rank path unless RPGP_LOWRANK=0, or RPGP_FACT_ASM is set: that variable
+    chooses between the exact sweep's kernels, so naming it asks for the sweep."""
+    env = os.environ
+    return env.get("RPGP_LOWRANK", "1") != "0" and "RPGP_FACT_ASM" not in env
+
 
 def mvm_sym_prepared(prep, V, scale, noise=0.0, j0=0, j1=None, out=None, shard=None):
-    """Factorised fast path: same result contract as mvm_sym for the Z that `prep` was built from."""
+    """Factorised fast path: same result contract as mvm_sym for the Z that `prep` was built from.  Served by the Chebyshev
+    low-rank form (rpgp_mvm_sym_lowrank_range) when the plan of `prep` has a rank, by the exact sweep otherwise."""
     world, rank = shard if shard is not None else (1, 0)
     lib = _lib.load()
     if not prep.fast_ok:
@@ -230,6 +269,14 @@ def mvm_sym_prepared(prep, V, scale, noise=0.0, j0=0, j1=None, out=None, shard=N
     T = V2.shape[1]
     if out is None:
         out = torch.empty_like(V2)
+    if lowrank_enabled() and prep.rank > 0:
+        with _on(prep.device):
+            nbytes = lib.rpgp_mvm_sym_lowrank_workspace_bytes(prep._handle, N, T)
+            ws = _workspace(prep.device, nbytes)
+            _lib.check(lib.rpgp_mvm_sym_lowrank_range(prep._handle, prep.buf.data_ptr(), V2.data_ptr(), out.data_ptr(), N,
+                                                      J, T, j0, j1, world, rank, float(scale), float(noise), ws.data_ptr(),
+                                                      ws.numel(), _stream()), "rpgp_mvm_sym_lowrank_range")
+        return out.squeeze(1) if squeeze else out
     with _on(prep.device):
         nbytes = lib.rpgp_mvm_sym_range_workspace_bytes(N, T, world, rank)
         ws = _workspace(prep.device, nbytes)
