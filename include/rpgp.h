@@ -143,6 +143,33 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
                                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Training tolerance and the low-rank bilinear derivative (same plan).
+ *   rpgp_lowrank_create_tol: rpgp_lowrank_create with the per-entry tail tolerance min(tol, 2^-26) (tol > 0).  A tail eps per
+ *     entry moves the operator by ||K~ - K||_2 <= N scale J eps, so a solve on scale K + sigma^2 I asks for
+ *     tol = 1e-3 sigma^2 / (scale J N) as well.
+ *   rpgp_lowrank_grad_select (host only, like rpgp_lowrank_select): the rank q of the antisymmetric Chebyshev coefficients D of
+ *     G(x, y) = -2 ln2 kappa h (x - y) exp2(-h^2 (x - y)^2)  (kappa = (2 ln 2)^-1/2), i.e. -(z - z') e(z, z') in z units:
+ *     the smallest q whose discarded tail sum_{max(m,n) >= q} |d_mn| is <= min(tol, 2^-26); 0 above q_max (<= 128).
+ *     `coef_host` (optional, q_max x q_max row-major) receives D.
+ *   rpgp_lowrank_grad_prepare: chooses q for the plan's h and stores D and the plan's own coefficients C (both float64) in the
+ *     caller's device buffer of RPGP_LOWRANK_GRAD_BYTES, which must outlive the handle's derivative calls.  *q_host = 0 (no derivative rank) when q > 64
+ *     or the plan has rank 1.  Synchronises the stream.  A later call replaces the rank.
+ *   rpgp_bilinear_grad_lowrank: rpgp_bilinear_grad's result contract (gZ for the columns [j0, j1) only — the others are not
+ *     touched —, gscale) on the plan's Z, any T, computed from the product form in four launches with float64 reductions in a
+ *     fixed order: repeated calls are bit-identical.  RPGP_EINVAL when the handle has no derivative rank.  Workspace:
+ *     rpgp_bilinear_grad_lowrank_workspace_bytes (0 without a derivative rank).
+ */
+#define RPGP_LOWRANK_GRAD_BYTES 65536
+int rpgp_lowrank_create_tol(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes,
+                            int *p_host, void **handle_host, void *stream);
+int rpgp_lowrank_grad_select(double h, int q_max, double tol, int *q_host, double *tail_host, double *coef_host);
+int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoef_bytes, int *q_host, void *stream);
+size_t rpgp_bilinear_grad_lowrank_workspace_bytes(const void *handle, int64_t N, int T);
+int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *R, float *gZ, float *gscale, int64_t N,
+                               int ldg, int T, int j0, int j1, float scale, void *workspace, size_t workspace_bytes,
+                               void *stream);
+
+/*
  * Rectangular fused MVM:  out = scale * sum_j K_j(Z1,Z2) @ V      (Z1: M x ., Z2: N x ., V: N x T, out: M x T)
  * Replaces K(X*,X) @ alpha and K(X,X*) blocks of the prediction strategy driven from training_routines.py:551-575.
  */
@@ -466,6 +493,8 @@ int rpgp_family_generic_bilinear(int dtype, int kind, int group, int ncomp, cons
 #define RPGP_OP_SUM 6             /* sum of G unsharded operators on the same N rows: prep -> rpgp_operator[G] in HOST memory (each
                                      part with its own scale / noise; no nesting) — the additive kernels whose multiplicative
                                      groups differ in size (general_rp_poly, training_routines.py:192-207) */
+#define RPGP_OP_LOWRANK 7         /* Chebyshev low-rank product (rpgp_mvm_sym_lowrank_range): prep = the plan HANDLE of
+                                     rpgp_lowrank_create[_tol]; N, J, j0, j1, scale, noise as for FUSED_PREPARED; unsharded only */
 typedef struct rpgp_operator {
   int kind;
   int64_t N;

@@ -15,6 +15,8 @@ class HipBackend:
     supports_padded_dense = True
     prepare = staticmethod(ops.Prepared)
     mvm_sym_prepared = staticmethod(ops.mvm_sym_prepared)
+    lowrank_train_plan = staticmethod(ops.lowrank_train_plan)
+    bilinear_grad_lowrank = staticmethod(ops.bilinear_grad_lowrank)
     mvm_rect = staticmethod(ops.mvm_rect)
     dense = staticmethod(ops.dense)
     bilinear_grad = staticmethod(ops.bilinear_grad)

@@ -899,6 +899,12 @@ int apply_operator(const rpgp_operator *op, const ShardCtx &sh, const float *V, 
                                          ws, ws_bytes, stream);
       }
       break;
+    case RPGP_OP_LOWRANK:
+      // (unsharded only; rpgp_mvm_sym_lowrank_range reads nothing behind its `prep` argument but checks it: the handle)
+      if (partial || world != 1) return RPGP_EINVAL;
+      rc = rpgp_mvm_sym_lowrank_range(op->prep, op->prep, V, out, op->N, op->J, T, op->j0, op->j1, 1, 0, op->scale, op->noise,
+                                      ws, ws_bytes, stream);
+      break;
     case RPGP_OP_SKI:
       if (sh.mode == RPGP_SHARD_ROWS) {
         const size_t nh = (size_t)op->J * op->G * T;
@@ -953,6 +959,8 @@ size_t operator_workspace(const rpgp_operator *op, int T) {
     case RPGP_OP_FUSED:
     case RPGP_OP_FUSED_PREPARED:
       return rpgp_mvm_sym_range_workspace_bytes(op->N, T, world, rank);
+    case RPGP_OP_LOWRANK:
+      return rpgp_mvm_sym_lowrank_workspace_bytes(op->prep, op->N, T);
     case RPGP_OP_SKI:
       return rpgp_ski_workspace_bytes(op->J, op->G, T);
     case RPGP_OP_DENSE:

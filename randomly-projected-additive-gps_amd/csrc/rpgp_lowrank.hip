@@ -12,6 +12,16 @@
 //   (a) project  W_j[n][t]  = sum_i T_n(x_ij) v_it           per (row block, projection, t): block partials
 //   (b) combine  U_j[m][t]  = scale * sum_n c_mn W_j[n][t]   per (projection, t): partials summed in a fixed order
 //   (c) output   out_it     = sum_j sum_m T_m(x_ij) U_j[m][t] (Clenshaw) + noise * v_it
+//
+// Bilinear derivative (rpgp_bilinear_grad's contract, S = L R^T + R L^T).  With g(x, y) = d f / dx, the factor of that
+// contract is  -(z_i - z_i') e(i, i') = (kappa / h) g(x_i, x_i')  (kappa = (2 ln 2)^-1/2: a = (z - mid) kappa), and
+//   G(x, y) = (kappa / h) g(x, y) = -2 ln2 kappa h (x - y) f(x, y) = sum_{m,n < q} d_mn T_m(x) T_n(y) + tail  (D antisymmetric)
+// in z units (|G| <= e^-1/2), chosen like C: the smallest q whose tail is <= the tolerance.  Four launches:
+//   (a) project  W^L_j, W^R_j as for the product (T(x)^T L, T(x)^T R, float64 block partials and, here, a float64
+//                Chebyshev recurrence), to rank max(p, q)
+//   (b) combine  U^R_j = scale D W^R_j, U^L_j = scale D W^L_j (float64), and gscale_jt = W^L_j[:,t]^T C W^R_j[:,t]
+//   (c) output   gZ_ij = sum_m T_m(x_ij) q_m,  q_m = sum_t L_it U^R_j[m][t] + R_it U^L_j[m][t]  (float64, one Clenshaw sum);
+//                the first workgroup also sums the gscale_jt in a fixed order
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -33,6 +43,7 @@ constexpr int kPrepMaxJ = 64;
 constexpr int kRefDegree = 128;          // reference degree of the 2-D Chebyshev interpolant (rank selection)
 constexpr int kMaxRank = 64;             // largest rank a plan serves (PB <= 64 floats of accumulators per lane)
 constexpr double kTailTol = 1.0 / (1 << 26);
+constexpr double kKappa = 0.84932180028801907;   // (2 ln 2)^-1/2
 constexpr int kProjRowsPerThread = 8;    // pass (a): 2 048 rows per workgroup
 constexpr int kProjRows = 256 * kProjRowsPerThread;
 constexpr int kOutRows = 64;             // pass (c): 64 rows x 4 projection groups per workgroup
@@ -44,6 +55,10 @@ struct LowrankPlan {
   double h, tail;
   const float *coef;                     // pb x pb, fp32, zero outside p x p
   const float *xt;                       // J x N coordinates x = a / h
+  int q = 0, qb = 0;                     // derivative rank and padded rank (0: no derivative, see rpgp_lowrank_grad_prepare)
+  const double *dcoef = nullptr;         // qb x qb, fp64 (in z units), zero outside q x q
+  const double *ccoef = nullptr;         // pb x pb, fp64: the coefficients whose fp32 rounding is `coef` (gscale)
+  double tol = 0.0;                      // the plan's tail tolerance
 };
 
 inline int pad8(int p) { return (p + 7) & ~7; }
@@ -51,8 +66,9 @@ inline int proj_blocks(int64_t N) { return (int)((N + kProjRows - 1) / kProjRows
 
 // ---- rank selection (host, double) ------------------------------------------------------------------------------
 // coefficients of the degree-(M-1) interpolant of f(x, y) = exp2(-h^2 (x - y)^2) at the M x M Chebyshev points of the
-// first kind (a separable DCT-II), c[m * M + n]
-void cheb2d_coefficients(double h, std::vector<double> &c) {
+// first kind (a separable DCT-II), c[m * M + n]; deriv: of G(x, y) = -2 ln2 kappa h (x - y) f(x, y) instead, made exactly
+// antisymmetric
+void cheb2d_coefficients(double h, std::vector<double> &c, bool deriv = false) {
   const int M = kRefDegree;
   std::vector<double> xs(M), cs((size_t)M * M), f((size_t)M * M), g((size_t)M * M);
   for (int k = 0; k < M; ++k) xs[k] = cos(M_PI * (k + 0.5) / M);
@@ -62,7 +78,13 @@ void cheb2d_coefficients(double h, std::vector<double> &c) {
   for (int k = 0; k < M; ++k)
     for (int l = 0; l <= k; ++l) {
       const double d = xs[k] - xs[l];
-      f[(size_t)k * M + l] = f[(size_t)l * M + k] = exp2(-h2 * d * d);
+      if (!deriv) {
+        f[(size_t)k * M + l] = f[(size_t)l * M + k] = exp2(-h2 * d * d);
+      } else {
+        const double v = -2.0 * M_LN2 * kKappa * h * d * exp2(-h2 * d * d);
+        f[(size_t)k * M + l] = v;
+        f[(size_t)l * M + k] = -v;
+      }
     }
   // g[k][n] = sum_l f[k][l] cos_n(l);  c[m][n] = sum_k cos_m(k) g[k][n]
   for (int k = 0; k < M; ++k)
@@ -80,14 +102,23 @@ void cheb2d_coefficients(double h, std::vector<double> &c) {
     const double wm = (m == 0 ? 1.0 : 2.0) / M;
     for (int n = 0; n < M; ++n) c[(size_t)m * M + n] *= wm * (n == 0 ? 1.0 : 2.0) / M;
   }
+  if (deriv)
+    for (int m = 0; m < M; ++m) {
+      c[(size_t)m * M + m] = 0.0;
+      for (int n = 0; n < m; ++n) {
+        const double a = 0.5 * (c[(size_t)m * M + n] - c[(size_t)n * M + m]);
+        c[(size_t)m * M + n] = a;
+        c[(size_t)n * M + m] = -a;
+      }
+    }
 }
 
 // smallest p with sum_{max(m,n) >= p} |c_mn| <= tol; 0 when the reference degree does not resolve f or p > p_max.
 // `tail` receives the bound of the chosen p (plus a rounding allowance of the fp64 transform).
-int select_rank(double h, int p_max, double tol, double *tail, std::vector<double> &c) {
+int select_rank(double h, int p_max, double tol, double *tail, std::vector<double> &c, bool deriv = false) {
   const int M = kRefDegree;
   if (!(h >= 0.0) || !isfinite(h)) return 0;
-  cheb2d_coefficients(h, c);
+  cheb2d_coefficients(h, c, deriv);
   // shell sums: s[q] = sum_{max(m,n) == q} |c_mn|
   std::vector<double> shell(M, 0.0);
   for (int m = 0; m < M; ++m)
@@ -279,6 +310,256 @@ int launch_lowrank(const LowrankPlan &P, const float *V, float *out, int N, int 
   return (int)hipGetLastError();
 }
 
+
+// ---- bilinear derivative ----------------------------------------------------------------------------------------
+// (a) lr_project_kernel with the Chebyshev recurrence in float64: near |x| = 1 the fp32 recurrence's error grows with m, which
+// the derivative (ranks up to 64, a bilinear gscale without the product's noise term) does not absorb.  Same layout and order.
+template <int PB>
+__global__ __launch_bounds__(256) void lrg_project_kernel(const float *__restrict__ xt, const float *__restrict__ V,
+                                                          double *__restrict__ part, int N, int T, int j0, int jn) {
+  __shared__ double red[4][PB];
+  const int b = blockIdx.x, jj = blockIdx.y, t = blockIdx.z;
+  const float *x = xt + (size_t)(j0 + jj) * N;
+  const int r0 = b * kProjRows + (int)threadIdx.x;
+  float xv[kProjRowsPerThread], vv[kProjRowsPerThread];
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {
+    const int i = r0 + u * 256;
+    const bool ok = i < N;
+    xv[u] = ok ? x[i] : 0.f;
+    vv[u] = ok ? V[(size_t)i * T + t] : 0.f;
+  }
+  double acc[PB];
+#pragma unroll
+  for (int m = 0; m < PB; ++m) acc[m] = 0.0;
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {
+    const double xi = xv[u], v = vv[u], x2 = 2.0 * xi;
+    double tm2 = 1.0, tm1 = xi;
+    acc[0] += v;
+    acc[1] = __builtin_fma(xi, v, acc[1]);
+#pragma unroll
+    for (int m = 2; m < PB; ++m) {
+      const double tm = __builtin_fma(x2, tm1, -tm2);
+      acc[m] = __builtin_fma(tm, v, acc[m]);
+      tm2 = tm1;
+      tm1 = tm;
+    }
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int m = 0; m < PB; ++m) {
+    const double s = wave_sum(acc[m]);
+    if (lane == 0) red[w][m] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    const int m = threadIdx.x;
+    part[(((size_t)b * jn + jj) * T + t) * PB + m] = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
+  }
+}
+
+// (b) per (projection, t): W^L, W^R summed over the row blocks in a fixed order (float64, as lr_combine_kernel), then
+//   U[jj][t][0][m] = scale sum_n d_mn W^R[n],  U[jj][t][1][m] = scale sum_n d_mn W^L[n]   (float64, m < QB)
+//   gsp[jj][t]     = sum_{m,n < p} W^L[m] c_mn W^R[n]   (the product's coefficients in float64, leading dimension pc)
+// partL / partR: [b][jj][t][PB] (PB >= QB and >= p).  grid (jn, T)
+template <int PB, int QB>
+__global__ __launch_bounds__(256) void lrg_combine_kernel(const double *__restrict__ partL, const double *__restrict__ partR,
+                                                          const double *__restrict__ dcoef, const double *__restrict__ ccoef,
+                                                          double *__restrict__ U, double *__restrict__ gsp, int nblk, int T,
+                                                          int jn, int p, int pc, double scale) {
+  constexpr int G = 256 / PB;
+  __shared__ double sw[2][G][PB];
+  __shared__ double w[2][PB];
+  __shared__ double cw[PB];
+  const int jj = blockIdx.x, t = blockIdx.y;
+  const int n = threadIdx.x % PB, g = threadIdx.x / PB;
+  if (g < G) {
+    double sl = 0.0, sr = 0.0;
+    for (int b = g; b < nblk; b += G) {
+      const size_t o = (((size_t)b * jn + jj) * T + t) * PB + n;
+      sl += partL[o];
+      sr += partR[o];
+    }
+    sw[0][g][n] = sl;
+    sw[1][g][n] = sr;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    double sl = sw[0][0][threadIdx.x], sr = sw[1][0][threadIdx.x];
+#pragma unroll
+    for (int k = 1; k < G; ++k) {
+      sl += sw[0][k][threadIdx.x];
+      sr += sw[1][k][threadIdx.x];
+    }
+    w[0][threadIdx.x] = sl;
+    w[1][threadIdx.x] = sr;
+  }
+  __syncthreads();
+  const int m = threadIdx.x;
+  if (m < QB) {
+    double ur = 0.0, ul = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < QB; ++k) {
+      const double d = dcoef[m * QB + k];
+      ur = __builtin_fma(d, w[1][k], ur);
+      ul = __builtin_fma(d, w[0][k], ul);
+    }
+    double *u = U + ((size_t)jj * T + t) * 2 * QB;
+    u[m] = scale * ur;
+    u[QB + m] = scale * ul;
+  }
+  if (m < PB) {                                           // (C W^R)[m], zero beyond p
+    double s = 0.0;
+    if (m < p)
+      for (int k = 0; k < p; ++k) s = __builtin_fma(ccoef[m * pc + k], w[1][k], s);
+    cw[m] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < p; ++k) s = __builtin_fma(w[0][k], cw[k], s);
+    gsp[(size_t)jj * T + t] = s;
+  }
+}
+
+// (c) gZ[i][j0 + jj] = sum_m T_m(x_ij) q_m,  q_m = sum_t L_it U[jj][t][0][m] + R_it U[jj][t][1][m]  (float64 fold, Clenshaw).
+// A workgroup: 64 rows x 4 waves, wave w takes jj = w, w + 4, ...; the results are staged in LDS and written row by row.
+// Workgroup (0, 0) also writes gscale = sum_jj sum_t gsp[jj][t] (fixed order).  grid (row blocks of 64)
+template <int QB>
+__global__ __launch_bounds__(256) void lrg_output_kernel(const float *__restrict__ xt, const double *__restrict__ U,
+                                                         const double *__restrict__ gsp, const float *__restrict__ L,
+                                                         const float *__restrict__ R, float *__restrict__ gZ,
+                                                         float *__restrict__ gscale, int N, int T, int j0, int jn, int ldg) {
+  __shared__ float sres[kOutRows][kPrepMaxJ + 1];
+  const int r = threadIdx.x & (kOutRows - 1);
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
+  const int row0 = blockIdx.x * kOutRows;
+  const int i = row0 + r;
+  const bool ok = i < N;
+  for (int jj = wv; jj < jn; jj += 4) {
+    const double *u = U + (size_t)jj * T * 2 * QB;
+    double q[QB];
+#pragma unroll
+    for (int m = 0; m < QB; ++m) q[m] = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const double l = ok ? (double)L[(size_t)i * T + t] : 0.0;
+      const double rr = ok ? (double)R[(size_t)i * T + t] : 0.0;
+      const double *ut = u + (size_t)t * 2 * QB;
+#pragma unroll
+      for (int m = 0; m < QB; ++m) q[m] = __builtin_fma(l, ut[m], __builtin_fma(rr, ut[QB + m], q[m]));
+    }
+    const double x = ok ? (double)xt[(size_t)(j0 + jj) * N + i] : 0.0, x2 = 2.0 * x;
+    double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = QB - 1; k >= 1; --k) {
+      const double bk = __builtin_fma(x2, b1, q[k] - b2);
+      b2 = b1;
+      b1 = bk;
+    }
+    sres[r][jj] = (float)__builtin_fma(x, b1, q[0] - b2);
+  }
+  __syncthreads();
+  const int rows = N - row0 < kOutRows ? N - row0 : kOutRows;
+  for (int e = threadIdx.x; e < rows * jn; e += 256) {
+    const int rr = e / jn, c = e - rr * jn;
+    gZ[(size_t)(row0 + rr) * ldg + j0 + c] = sres[rr][c];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < jn * T; ++k) s += gsp[k];
+    *gscale = (float)s;
+  }
+}
+
+inline int grad_pb(const LowrankPlan &P) { return pad8(P.q > P.p ? P.q : P.p); }
+
+// workspace of the derivative: partL, partR (nblk x jn x T x PB doubles each), U (jn x T x 2 x QB doubles), gsp (jn x T)
+inline size_t grad_ws_bytes(const LowrankPlan &P, int64_t N, int jn, int T) {
+  return ((size_t)proj_blocks(N) * jn * T * grad_pb(P) * 2 + (size_t)jn * T * 2 * P.qb + (size_t)jn * T) * sizeof(double);
+}
+
+template <int PB, int QB>
+int launch_grad(const LowrankPlan &P, const float *L, const float *R, float *gZ, float *gscale, int N, int ldg, int T,
+                int j0, int jn, float scale, void *ws, hipStream_t st) {
+  const int nblk = proj_blocks(N);
+  const size_t np = (size_t)nblk * jn * T * PB;
+  double *partL = reinterpret_cast<double *>(ws), *partR = partL + np;
+  double *U = partR + np, *gsp = U + (size_t)jn * T * 2 * QB;
+  hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, L, partL, N, T, j0, jn);
+  hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, R, partR, N, T, j0, jn);
+  hipLaunchKernelGGL((lrg_combine_kernel<PB, QB>), dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, U, gsp, nblk, T,
+                     jn, P.p, P.pb, (double)scale);
+  hipLaunchKernelGGL(lrg_output_kernel<QB>, dim3((N + kOutRows - 1) / kOutRows), dim3(256), 0, st, P.xt, U, gsp, L, R, gZ,
+                     gscale, N, T, j0, jn, ldg);
+  return (int)hipGetLastError();
+}
+
+// (PB < QB never occurs: PB = pad8(max(p, q)) >= QB)
+template <int PB, int QB>
+int launch_grad_if(const LowrankPlan &P, const float *L, const float *R, float *gZ, float *gscale, int N, int ldg, int T,
+                   int j0, int jn, float scale, void *ws, hipStream_t st) {
+  if constexpr (PB >= QB) return launch_grad<PB, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+  return RPGP_EINVAL;
+}
+
+template <int QB>
+int dispatch_grad_pb(const LowrankPlan &P, const float *L, const float *R, float *gZ, float *gscale, int N, int ldg, int T,
+                     int j0, int jn, float scale, void *ws, hipStream_t st) {
+  switch (grad_pb(P)) {
+    case 8: return launch_grad_if<8, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 16: return launch_grad_if<16, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 24: return launch_grad_if<24, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 32: return launch_grad_if<32, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 40: return launch_grad_if<40, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 48: return launch_grad_if<48, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 56: return launch_grad_if<56, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    case 64: return launch_grad_if<64, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
+    default: return RPGP_EINVAL;
+  }
+}
+
+// the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
+int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes, int *p_host,
+                void **handle_host, void *stream) {
+  if (!prep || !plan || !p_host || !handle_host || N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ)
+    return RPGP_EINVAL;
+  if (plan_bytes < rpgp_lowrank_plan_bytes(N, J)) return RPGP_EWORKSPACE;
+  *p_host = 0;
+  *handle_host = nullptr;
+  // a slightly wider interval than max|a| absorbs the rounding of a = (z - mid) * c at the ends of the range
+  const double h = (double)max_abs * (1.0 + 1.0 / (1 << 20));
+  std::vector<double> c;
+  double tail = 0.0;
+  const int p = select_rank(h, kMaxRank, tol, &tail, c);
+  if (p == 0) return 0;                                   // not served: the sweep runs
+  const int pb = pad8(p);
+  std::vector<float> cf((size_t)pb * pb, 0.f);
+  for (int m = 0; m < p; ++m)
+    for (int n = 0; n < p; ++n) cf[(size_t)m * pb + n] = (float)c[(size_t)m * kRefDegree + n];
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  float *coef = reinterpret_cast<float *>(plan);
+  float *xt = coef + (size_t)kMaxRank * kMaxRank;
+  hipError_t e = hipMemcpyAsync(coef, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return (int)e;
+  // (rank 1: T_0 = 1 whatever x is; h = 0 would divide by zero)
+  const float inv_h = (p == 1 || !(h > 0.0)) ? 0.f : (float)(1.0 / h);
+  const long long total = N * J;
+  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+  const float2v *rowdat = reinterpret_cast<const float2v *>(reinterpret_cast<const float *>(prep) + kPrepRowdatOffsetFloats);
+  hipLaunchKernelGGL(lr_coords_kernel, dim3(blocks), dim3(256), 0, st, rowdat, xt, (long long)N, J, inv_h);
+  int rc = (int)hipGetLastError();
+  if (rc) return rc;
+  e = hipStreamSynchronize(st);                           // (the host copy of the coefficients goes out of scope)
+  if (e != hipSuccess) return (int)e;
+  LowrankPlan *P = new (std::nothrow) LowrankPlan{p, pb, N, J, h, tail, coef, xt};
+  if (!P) return RPGP_EINVAL;
+  P->tol = tol;
+  *p_host = p;
+  *handle_host = P;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -303,41 +584,13 @@ size_t rpgp_lowrank_plan_bytes(int64_t N, int J) {
 
 int rpgp_lowrank_create(const void *prep, int64_t N, int J, float max_abs, void *plan, size_t plan_bytes, int *p_host,
                         void **handle_host, void *stream) {
-  if (!prep || !plan || !p_host || !handle_host || N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ)
-    return RPGP_EINVAL;
-  if (plan_bytes < rpgp_lowrank_plan_bytes(N, J)) return RPGP_EWORKSPACE;
-  *p_host = 0;
-  *handle_host = nullptr;
-  // a slightly wider interval than max|a| absorbs the rounding of a = (z - mid) * c at the ends of the range
-  const double h = (double)max_abs * (1.0 + 1.0 / (1 << 20));
-  std::vector<double> c;
-  double tail = 0.0;
-  const int p = select_rank(h, kMaxRank, kTailTol, &tail, c);
-  if (p == 0) return 0;                                   // not served: the sweep runs
-  const int pb = pad8(p);
-  std::vector<float> cf((size_t)pb * pb, 0.f);
-  for (int m = 0; m < p; ++m)
-    for (int n = 0; n < p; ++n) cf[(size_t)m * pb + n] = (float)c[(size_t)m * kRefDegree + n];
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  float *coef = reinterpret_cast<float *>(plan);
-  float *xt = coef + (size_t)kMaxRank * kMaxRank;
-  hipError_t e = hipMemcpyAsync(coef, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return (int)e;
-  // (rank 1: T_0 = 1 whatever x is; h = 0 would divide by zero)
-  const float inv_h = (p == 1 || !(h > 0.0)) ? 0.f : (float)(1.0 / h);
-  const long long total = N * J;
-  const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  const float2v *rowdat = reinterpret_cast<const float2v *>(reinterpret_cast<const float *>(prep) + kPrepRowdatOffsetFloats);
-  hipLaunchKernelGGL(lr_coords_kernel, dim3(blocks), dim3(256), 0, st, rowdat, xt, (long long)N, J, inv_h);
-  int rc = (int)hipGetLastError();
-  if (rc) return rc;
-  e = hipStreamSynchronize(st);                           // (the host copy of the coefficients goes out of scope)
-  if (e != hipSuccess) return (int)e;
-  LowrankPlan *P = new (std::nothrow) LowrankPlan{p, pb, N, J, h, tail, coef, xt};
-  if (!P) return RPGP_EINVAL;
-  *p_host = p;
-  *handle_host = P;
-  return 0;
+  return create_plan(prep, N, J, max_abs, kTailTol, plan, plan_bytes, p_host, handle_host, stream);
+}
+
+int rpgp_lowrank_create_tol(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes,
+                            int *p_host, void **handle_host, void *stream) {
+  if (!(tol > 0.0)) return RPGP_EINVAL;
+  return create_plan(prep, N, J, max_abs, tol < kTailTol ? tol : kTailTol, plan, plan_bytes, p_host, handle_host, stream);
 }
 
 int rpgp_lowrank_destroy(void *handle) {
@@ -383,6 +636,86 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
   if (prof) {
     const int pc = rpgp_internal::prof_close(st);
     if (!rc) rc = pc;
+  }
+  return rc;
+}
+
+int rpgp_lowrank_grad_select(double h, int q_max, double tol, int *q_host, double *tail_host, double *coef_host) {
+  if (!q_host || q_max < 1 || q_max > kRefDegree || !(tol > 0.0)) return RPGP_EINVAL;
+  std::vector<double> c;
+  double tail = 0.0;
+  const int q = select_rank(h, q_max, tol < kTailTol ? tol : kTailTol, &tail, c, true);
+  *q_host = q;
+  if (tail_host) *tail_host = q ? tail : 0.0;
+  if (coef_host && q)
+    for (int m = 0; m < q; ++m)
+      for (int n = 0; n < q; ++n) coef_host[(size_t)m * q_max + n] = c[(size_t)m * kRefDegree + n];
+  return 0;
+}
+
+int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoef_bytes, int *q_host, void *stream) {
+  LowrankPlan *P = reinterpret_cast<LowrankPlan *>(handle);
+  if (!P || !dcoef || !q_host || !(tol > 0.0)) return RPGP_EINVAL;
+  if (dcoef_bytes < (size_t)RPGP_LOWRANK_GRAD_BYTES) return RPGP_EWORKSPACE;
+  *q_host = 0;
+  P->q = P->qb = 0;
+  P->dcoef = nullptr;
+  std::vector<double> c;
+  double tail = 0.0;
+  const int q = select_rank(P->h, kMaxRank, tol < kTailTol ? tol : kTailTol, &tail, c, true);
+  // (a rank-1 plan stores x = 0: it cannot evaluate a derivative of rank > 1)
+  if (q == 0 || (P->p == 1 && q > 1)) return 0;
+  const int qb = pad8(q);
+  // [D: qb x qb][C: pb x pb at 32 KiB], both float64; C is the plan's own selection again (same h, tolerance: same p)
+  std::vector<double> d((size_t)qb * qb, 0.0), cc((size_t)P->pb * P->pb, 0.0), cf;
+  for (int m = 0; m < q; ++m)
+    for (int n = 0; n < q; ++n) d[(size_t)m * qb + n] = c[(size_t)m * kRefDegree + n];
+  if (select_rank(P->h, kMaxRank, P->tol, nullptr, cf) != P->p) return RPGP_EINVAL;
+  for (int m = 0; m < P->p; ++m)
+    for (int n = 0; n < P->p; ++n) cc[(size_t)m * P->pb + n] = cf[(size_t)m * kRefDegree + n];
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  double *dd = reinterpret_cast<double *>(dcoef), *dc = dd + kMaxRank * kMaxRank;
+  hipError_t e = hipMemcpyAsync(dd, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return (int)e;
+  e = hipMemcpyAsync(dc, cc.data(), cc.size() * sizeof(double), hipMemcpyHostToDevice, st);
+  if (e != hipSuccess) return (int)e;
+  e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  P->q = q;
+  P->qb = qb;
+  P->dcoef = dd;
+  P->ccoef = dc;
+  *q_host = q;
+  return 0;
+}
+
+size_t rpgp_bilinear_grad_lowrank_workspace_bytes(const void *handle, int64_t N, int T) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P || !P->q || N <= 0 || N > 0x7fffffffLL || T <= 0) return 0;
+  return grad_ws_bytes(*P, N, P->J, T);
+}
+
+int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *R, float *gZ, float *gscale, int64_t N,
+                               int ldg, int T, int j0, int j1, float scale, void *workspace, size_t workspace_bytes,
+                               void *stream) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P || !L || !R || !gZ || !gscale || N <= 0 || T <= 0 || T > 65535) return RPGP_EINVAL;
+  if (N != P->N || j0 < 0 || j1 <= j0 || j1 > P->J || ldg < P->J) return RPGP_EINVAL;
+  if (!P->q) return RPGP_EINVAL;                          // no derivative rank: the caller runs rpgp_bilinear_grad
+  if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int n = (int)N, jn = j1 - j0;
+  int rc;
+  switch (P->qb) {
+    case 8: rc = dispatch_grad_pb<8>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 16: rc = dispatch_grad_pb<16>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 24: rc = dispatch_grad_pb<24>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 32: rc = dispatch_grad_pb<32>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 40: rc = dispatch_grad_pb<40>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 48: rc = dispatch_grad_pb<48>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 56: rc = dispatch_grad_pb<56>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    case 64: rc = dispatch_grad_pb<64>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
+    default: return RPGP_EINVAL;
   }
   return rc;
 }

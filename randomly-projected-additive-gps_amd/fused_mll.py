@@ -238,7 +238,11 @@ class _FusedMLL(torch.autograd.Function):
             if type(op) is AdditiveRPOperator and (op.shard is None or op.shard.world_size <= 1):
                 # (the plain operator's `_bilinear_derivative` is this call followed by `gs * weight`: the weight rides into the
                 #  chain-rule kernel instead of being one more launch)
-                gZ, gs = be.bilinear_grad(op.Z1.detach(), left, right, op._scale)
+                lr = op.lowrank_form() if op.lowrank_served else None     # (the solve decided the form of this step)
+                if lr is not None:
+                    gZ, gs = be.bilinear_grad_lowrank(lr, left, right, op._scale)
+                else:
+                    gZ, gs = be.bilinear_grad(op.Z1.detach(), left, right, op._scale)
                 gs_scale = op.weight
             else:
                 gZ, gs = op._bilinear_derivative(left, right)

@@ -86,6 +86,9 @@ def solve_operator(op, khat, Z, noise_f, width):
     matmul = khat._matmul
     native_op = khat
     sharded = op.shard is not None and op.shard.world_size > 1
+    if settings.lowrank_kernel.on() and getattr(op, "lowrank_form", None) is not None and \
+            op.lowrank_form(noise_f) is not None:
+        return matmul, native_op, sharded          # the low-rank form (RPGP_OP_LOWRANK): no cache to build
     if not isinstance(op, SKIAdditiveOperator) and Z.dtype == torch.float32:
         per_rank = 2.0 / (op.shard.world_size if sharded else 1)
         cache = op.to_symcache(wide=width > 4) if hasattr(op, "to_symcache") and \

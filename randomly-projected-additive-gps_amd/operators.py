@@ -104,6 +104,7 @@ class AdditiveRPOperator(LinearOperator):
         # with the noise in ONE device-to-host copy per optimiser step)
         self._scale_value = None
         self._prep = None          # rpgp_prepare tables for the factorised fast path (built on first use)
+        self._lowrank = None       # settings.lowrank_kernel: None undecided, False the sweep, else the ops.LowrankTrainPlan
 
     @property
     def _scale(self):
@@ -180,6 +181,38 @@ class AdditiveRPOperator(LinearOperator):
             return None
         return be.pivoted_cholesky(self.Z1.detach().contiguous(), self._scale, min(rank, self.Z1.shape[0]))
 
+    def lowrank_form(self, noise=None):
+        """The training plan of the Chebyshev low-rank form that serves this operator's solves and derivative
+        (settings.lowrank_kernel), or None for the exact sweep.  Decided ONCE per operator (= per hyper-parameter step) from
+        N, the scale and the noise (default: the host value the marginal likelihood recorded), so that the solve and the
+        derivative of a step use the same form."""
+        if getattr(self, "_lowrank", None) is None:
+            self._lowrank = False
+            be = _backend.get_backend()
+            plan_fn, prepare = getattr(be, "lowrank_train_plan", None), getattr(be, "prepare", None)
+            if noise is None:
+                noise = getattr(self, "_noise_host", None)
+            if settings.lowrank_kernel.on() and type(self) is AdditiveRPOperator and self.symmetric and \
+                    (self.shard is None or self.shard.world_size <= 1) and self.Z1.dtype == torch.float32 and \
+                    plan_fn is not None and prepare is not None and noise is not None and self.num_projections <= 64:
+                if self._prep is None:
+                    self._prep = prepare(self.Z1.detach())
+                plan = plan_fn(self._prep, self._scale, float(noise))
+                if plan is not None:
+                    self._lowrank = plan
+        return self._lowrank or None
+
+    @property
+    def lowrank_served(self):
+        """Whether the low-rank form serves this operator (False while undecided)."""
+        return bool(getattr(self, "_lowrank", None))
+
+    @property
+    def lowrank_ranks(self):
+        """(p, q) of the low-rank form that serves this operator, or None."""
+        lr = getattr(self, "_lowrank", None)
+        return (lr.p, lr.q) if lr else None
+
     def native_descriptor(self, noise=0.0):
         """`struct rpgp_operator` for the native mBCG executor, or None when the operator must stay on the Python path
         (rectangular, float64, or a backend without the executor).  A sharded operator describes THIS RANK's share —
@@ -193,6 +226,9 @@ class AdditiveRPOperator(LinearOperator):
             return None
         from . import _lib
         z1 = self.Z1.detach()
+        lr = self.lowrank_form(noise) if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        if lr is not None:
+            return be.make_operator_desc(_lib.RPGP_OP_LOWRANK, z1.shape[0], z1.shape[1], self._scale, noise, lowrank=lr)
         j0, j1 = self._jrange()
         kw = {}
         if sharded:
@@ -274,7 +310,10 @@ class AdditiveRPOperator(LinearOperator):
             raise NotImplementedError("derivatives are only needed for the train-train kernel")
         be = _backend.get_backend()
         j0, j1 = self._jrange()
-        if j1 > j0:
+        lr = self.lowrank_form() if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        if lr is not None:
+            gZ, gs = be.bilinear_grad_lowrank(lr, left_vecs.detach(), right_vecs.detach(), self._scale)
+        elif j1 > j0:
             gZ, gs = be.bilinear_grad(self.Z1.detach(), left_vecs.detach(), right_vecs.detach(), self._scale,
                                       j0=j0, j1=j1)
         else:

@@ -255,6 +255,102 @@ def lowrank_enabled():
     return env.get("RPGP_LOWRANK", "1") != "0" and "RPGP_FACT_ASM" not in env
 
 
+_LOWRANK_TAIL = 2.0 ** -26
+
+
+def lowrank_train_tol(N, J, scale, noise):
+    """Per-entry tail tolerance of the training plan: a tail eps moves scale K by ||K~ - K||_2 <= N scale J eps, which the solve
+    on scale K + noise I must see as <= 1e-3 noise, and eps <= 2^-26 (the product's own bound) in any case.  0: no noise, not served."""
+    if not (noise > 0.0) or not (scale > 0.0):
+        return 0.0
+    return min(_LOWRANK_TAIL, 1e-3 * noise / (scale * J * N))
+
+
+def lowrank_grad_select(h, q_max=64, tol=_LOWRANK_TAIL):
+    """(q, tail, D) of rpgp_lowrank_grad_select (host only): D (q x q float64, antisymmetric) of -(z - z') e(z, z') in z units
+    on x = a / h; q = 0 above q_max."""
+    import ctypes
+    import numpy as np
+    lib = _lib.load()
+    q, tail = ctypes.c_int(0), ctypes.c_double(0.0)
+    D = np.zeros((q_max, q_max), dtype=np.float64)
+    _lib.check(lib.rpgp_lowrank_grad_select(float(h), int(q_max), float(tol), ctypes.byref(q), ctypes.byref(tail),
+                                            D.ctypes.data), "rpgp_lowrank_grad_select")
+    q = int(q.value)
+    return q, float(tail.value), D[:q, :q].copy()
+
+
+class LowrankTrainPlan:
+    """Training plan of one Prepared (rpgp_lowrank_create_tol + rpgp_lowrank_grad_prepare at one tolerance): the product
+    (RPGP_OP_LOWRANK) and the derivative (rpgp_bilinear_grad_lowrank) of the same low-rank form.  p, q: ranks (0: not served)."""
+
+    def __init__(self, prep, tol):
+        import ctypes
+        lib = _lib.load()
+        self.N, self.J, self.device, self.tol = prep.N, prep.J, prep.device, float(tol)
+        self.p = self.q = 0
+        self.handle = None
+        with _on(prep.device):
+            self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes(self.N, self.J)), dtype=torch.uint8, device=self.device)
+            p, h = ctypes.c_int(0), ctypes.c_void_p(None)
+            _lib.check(lib.rpgp_lowrank_create_tol(prep.buf.data_ptr(), self.N, self.J, prep.max_abs, self.tol,
+                                                   self._plan.data_ptr(), self._plan.numel(), ctypes.byref(p),
+                                                   ctypes.byref(h), _stream()), "rpgp_lowrank_create_tol")
+            self.p, self.handle = int(p.value), h.value
+            if self.p:
+                self._dcoef = torch.empty(_lib.RPGP_LOWRANK_GRAD_BYTES, dtype=torch.uint8, device=self.device)
+                q = ctypes.c_int(0)
+                _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(), self._dcoef.numel(),
+                                                         ctypes.byref(q), _stream()), "rpgp_lowrank_grad_prepare")
+                self.q = int(q.value)
+
+    @property
+    def served(self):
+        return self.p > 0 and self.q > 0
+
+    def __del__(self):
+        if getattr(self, "handle", None):
+            _lib.load().rpgp_lowrank_destroy(self.handle)
+            self.handle = None
+
+
+def lowrank_train_plan(prep, scale, noise):
+    """The training plan of `prep` for this step's (N, scale, noise), or None when the low-rank form does not serve it (switch
+    off, not fast_ok, no tolerance, or p or q above 64).  Built once per Prepared and tolerance."""
+    if not lowrank_enabled() or not prep.fast_ok:
+        return None
+    tol = lowrank_train_tol(prep.N, prep.J, scale, noise)
+    if not tol:
+        return None
+    cached = getattr(prep, "_train", None)
+    if cached is None or cached.tol != tol:
+        cached = prep._train = LowrankTrainPlan(prep, tol)
+    return cached if cached.served else None
+
+
+def bilinear_grad_lowrank(plan, L, R, scale, j0=0, j1=None):
+    """(gZ [N x J], gscale [scalar tensor]) of bilinear_grad on the plan's Z, from the low-rank form (rpgp_bilinear_grad_lowrank).
+    The columns outside [j0, j1) are zero."""
+    lib = _lib.load()
+    N, J = plan.N, plan.J
+    j1 = J if j1 is None else j1
+    L2, _ = _as_matrix(L, N, "L")
+    R2, _ = _as_matrix(R, N, "R")
+    if L2.shape != R2.shape:
+        raise ValueError("L and R must have the same shape")
+    T = L2.shape[1]
+    full = j0 == 0 and j1 == J
+    gZ = (torch.empty if full else torch.zeros)((N, J), dtype=torch.float32, device=plan.device)
+    gs = torch.empty((), dtype=torch.float32, device=plan.device)
+    with _on(plan.device):
+        nbytes = lib.rpgp_bilinear_grad_lowrank_workspace_bytes(plan.handle, N, T)
+        ws = _workspace(plan.device, nbytes)
+        _lib.check(lib.rpgp_bilinear_grad_lowrank(plan.handle, L2.data_ptr(), R2.data_ptr(), gZ.data_ptr(), gs.data_ptr(), N,
+                                                  J, T, j0, j1, float(scale), ws.data_ptr(), ws.numel(), _stream()),
+                   "rpgp_bilinear_grad_lowrank")
+    return gZ, gs
+
+
 def mvm_sym_prepared(prep, V, scale, noise=0.0, j0=0, j1=None, out=None, shard=None):
     """Factorised fast path: same result contract as mvm_sym for the Z that `prep` was built from.  Served by the Chebyshev
     low-rank form (rpgp_mvm_sym_lowrank_range) when the plan of `prep` has a rank, by the exact sweep otherwise."""
@@ -1174,9 +1270,10 @@ def family_bilinear_grad_dense(fam, Z, S, scale):
 
 
 def make_operator_desc(kind, N, J, scale, noise, Z=None, prep=None, gp=None, j0=0, j1=None, G=0, Kd=None, family=None,
-                       symcache=None, world=1, rank=0):
+                       symcache=None, world=1, rank=0, lowrank=None):
     """Fill a `struct rpgp_operator`; returns (struct, keepalive) — keep both referenced while the solve runs.
-    (world, rank): this rank's pair-shard of the fused / prepared operator (a symcache carries its own)."""
+    (world, rank): this rank's pair-shard of the fused / prepared operator (a symcache carries its own).  `lowrank`: the
+    LowrankTrainPlan of RPGP_OP_LOWRANK (its handle travels in `prep`)."""
     import ctypes
     d = _lib.RpgpOperator()
     d.kind, d.N, d.J, d.ldz = kind, N, J, J
@@ -1192,7 +1289,9 @@ def make_operator_desc(kind, N, J, scale, noise, Z=None, prep=None, gp=None, j0=
     if symcache is not None:                       # RPGP_OP_SYMCACHE: the cache travels in (Kd, ldk = bytes, G = layout)
         d.Kd, d.ldk, d.G = symcache.buf.data_ptr(), symcache.nbytes, symcache.layout
         d.world, d.rank = symcache.world, symcache.rank
-    return d, (Z, prep, gp, Kd, family, symcache)
+    if lowrank is not None:
+        d.prep = lowrank.handle
+    return d, (Z, prep, gp, Kd, family, symcache, lowrank)
 
 
 def make_sum_operator_desc(parts):

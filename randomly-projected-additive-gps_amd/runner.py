@@ -246,6 +246,8 @@ def build_parser():
                    help="(rpgp) always materialise K once per hyper-parameter step when it fits in HBM (default: auto)")
     p.add_argument("--no_cache_kernel", dest="cache_kernel", action="store_const", const=False,
                    help="(rpgp) never materialise K: every CG iteration runs the fused recompute-in-kernel MVM")
+    p.add_argument("--lowrank_kernel", action="store_true",
+                   help="(rpgp) train and solve the exact kernel through its Chebyshev low-rank form where its ranks fit")
     return p
 
 
@@ -396,7 +398,8 @@ def main(argv=None, rank_entry=None):
                 settings.use_toeplitz(args.use_toeplitz), settings.max_cg_iterations(args.max_cg_iterations), \
                 settings.beta_features.checkpoint_kernel(args.checkpoint_kernel), \
                 settings.skip_logdet_forward(args.skip_log_det_forward), \
-                settings.memory_efficient(args.memory_efficient), settings.cache_kernel(args.cache_kernel):
+                settings.memory_efficient(args.memory_efficient), settings.cache_kernel(args.cache_kernel), \
+                settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)):
             if args.ablation:
                 if args.k is not None:
                     abl_vars = args.k

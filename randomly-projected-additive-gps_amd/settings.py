@@ -132,6 +132,11 @@ comm_backend = _setting("comm_backend", "rccl")
 # the native mBCG executor also serves sharded operators (partial products / row blocks summed by the reducer's hook on
 # the launch stream); False sends sharded solves through the torch-op loop of linear_cg.py
 native_sharded_cg = _setting("native_sharded_cg", True, flag=True)
+# training and its solves on the Chebyshev low-rank form of the exact kernel (csrc/rpgp_lowrank.hip): an unsharded float32
+# additive-RP operator whose plan at the training tolerance (per-entry tail <= min(2^-26, 1e-3 noise / (scale J N))) has ranks
+# p, q <= 64 is solved through RPGP_OP_LOWRANK (no packed / dense cache) and differentiated by rpgp_bilinear_grad_lowrank — both
+# or neither, decided once per operator.  Off: the exact sweep.  RPGP_LOWRANK=0 and RPGP_FACT_ASM keep the sweep either way.
+lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
 
 
 class fast_computations:
