@@ -17,6 +17,8 @@ class HipBackend:
     mvm_sym_prepared = staticmethod(ops.mvm_sym_prepared)
     lowrank_train_plan = staticmethod(ops.lowrank_train_plan)
     bilinear_grad_lowrank = staticmethod(ops.bilinear_grad_lowrank)
+    lowrank_post_select = staticmethod(ops.lowrank_post_select)
+    lowrank_features = staticmethod(ops.lowrank_features)
     mvm_rect = staticmethod(ops.mvm_rect)
     dense = staticmethod(ops.dense)
     bilinear_grad = staticmethod(ops.bilinear_grad)

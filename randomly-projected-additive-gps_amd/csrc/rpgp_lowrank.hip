@@ -519,6 +519,105 @@ int dispatch_grad_pb(const LowrankPlan &P, const float *L, const float *R, float
   }
 }
 
+// ---- explicit features of the posterior (rpgp_lowrank_post_select / rpgp_lowrank_features_f64) --------------------------
+// C (p x p, symmetric PSD up to rounding: a congruence of the kernel's Gram matrix at the Chebyshev points) = Q diag(l) Q^T by
+// cyclic Jacobi rotations in double (a fixed sweep order: deterministic).  a: p x p row-major, overwritten; q: eigenvectors as
+// columns (p x p row-major); l: eigenvalues.
+void jacobi_eigh(std::vector<double> &a, int p, std::vector<double> &q, std::vector<double> &l) {
+  q.assign((size_t)p * p, 0.0);
+  for (int i = 0; i < p; ++i) q[(size_t)i * p + i] = 1.0;
+  for (int sweep = 0; sweep < 64; ++sweep) {
+    double off = 0.0, diag = 0.0;
+    for (int i = 0; i < p; ++i) {
+      diag += a[(size_t)i * p + i] * a[(size_t)i * p + i];
+      for (int j = i + 1; j < p; ++j) off += a[(size_t)i * p + j] * a[(size_t)i * p + j];
+    }
+    if (off <= 1e-34 * diag || off == 0.0) break;
+    for (int i = 0; i < p - 1; ++i)
+      for (int j = i + 1; j < p; ++j) {
+        const double aij = a[(size_t)i * p + j];
+        if (aij == 0.0) continue;
+        const double aii = a[(size_t)i * p + i], ajj = a[(size_t)j * p + j];
+        const double theta = (ajj - aii) / (2.0 * aij);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        for (int k = 0; k < p; ++k) {                     // A <- A R (columns i, j), then A <- R^T A (rows i, j)
+          const double aki = a[(size_t)k * p + i], akj = a[(size_t)k * p + j];
+          a[(size_t)k * p + i] = c * aki - s * akj;
+          a[(size_t)k * p + j] = s * aki + c * akj;
+        }
+        for (int k = 0; k < p; ++k) {
+          const double aik = a[(size_t)i * p + k], ajk = a[(size_t)j * p + k];
+          a[(size_t)i * p + k] = c * aik - s * ajk;
+          a[(size_t)j * p + k] = s * aik + c * ajk;
+        }
+        for (int k = 0; k < p; ++k) {
+          const double qki = q[(size_t)k * p + i], qkj = q[(size_t)k * p + j];
+          q[(size_t)k * p + i] = c * qki - s * qkj;
+          q[(size_t)k * p + j] = s * qki + c * qkj;
+        }
+      }
+  }
+  l.resize(p);
+  for (int i = 0; i < p; ++i) l[i] = a[(size_t)i * p + i];
+}
+
+constexpr int kFeatRows = 64;            // rows per workgroup (4 waves x 16 rows, all projections)
+constexpr int kFeatLd = 80;              // LDS row stride of G in doubles: rows 4s + kq of one read land 32 banks apart
+
+typedef double double4v __attribute__((ext_vector_type(4)));
+
+// B[i ldb + j r + k] = sqrt_scale * sum_{m < p} T_m(x_ij) G[m r + k],  x_ij = (Z[i ldz + j] - mid[j]) inv_w.
+// G (zero-padded to PB x 64) is staged in LDS once per workgroup; a wave takes 16 rows and, for each projection, forms the
+// (16 x PB) Chebyshev tile in registers (lane l: row l & 15, T_m for m = 4s + (l >> 4)) and multiplies it by G's column
+// tiles of 16 on v_mfma_f64_16x16x4_f64 (A[row l&15][k l>>4], B[k l>>4][col l&15]; D col l&15, row (l>>4) + 4 reg).
+// Every store: 4 rows x 16 consecutive doubles.  grid (ceil(N / 64))
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
+                                                          const double *__restrict__ mid, double inv_w,
+                                                          const double *__restrict__ G, int p, int r, double sqrt_scale,
+                                                          double *__restrict__ B, long long ldb) {
+  __shared__ double gs[PB * kFeatLd];
+  for (int e = threadIdx.x; e < PB * 64; e += 256) {
+    const int m = e >> 6, k = e & 63;
+    gs[m * kFeatLd + k] = (m < p && k < r) ? G[m * r + k] : 0.0;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c16 = lane & 15, kq = lane >> 4;
+  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
+  const long long row = rbase + c16;
+  const bool ok = row < N;
+  const int nct = (r + 15) >> 4;
+  for (int j = 0; j < J; ++j) {
+    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0, x2 = 2.0 * x;
+    double a[PB / 4];
+    double tm2 = 1.0, tm1 = x;
+    a[0] = kq == 0 ? 1.0 : (kq == 1 ? x : 0.0);
+#pragma unroll
+    for (int m = 2; m < PB; ++m) {                        // T_m = 2x T_{m-1} - T_{m-2}; lane keeps m = 4s + kq
+      const double tm = __builtin_fma(x2, tm1, -tm2);
+      if ((m & 3) == kq) a[m >> 2] = tm;
+      tm2 = tm1;
+      tm1 = tm;
+    }
+    for (int ct = 0; ct < nct; ++ct) {
+      double4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < PB / 4; ++s)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gs[(4 * s + kq) * kFeatLd + ct * 16 + c16], acc, 0, 0, 0);
+      const int col = ct * 16 + c16;
+      if (col < r) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long long ro = rbase + kq + 4 * i;
+          if (ro < N) B[ro * ldb + (long long)j * r + col] = sqrt_scale * acc[i];
+        }
+      }
+    }
+  }
+}
+
 // the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
 int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes, int *p_host,
                 void **handle_host, void *stream) {
@@ -718,6 +817,82 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
     default: return RPGP_EINVAL;
   }
   return rc;
+}
+
+int rpgp_lowrank_post_select(double h, double tol, int p_max, int *p_host, int *r_host, double *tail_host, double *G_host) {
+  if (!p_host || !r_host || p_max < 1 || p_max > kRefDegree || !(tol > 0.0)) return RPGP_EINVAL;
+  *p_host = *r_host = 0;
+  if (tail_host) *tail_host = 0.0;
+  std::vector<double> c;
+  double tail = 0.0;
+  const int p = select_rank(h, p_max, tol, &tail, c);
+  if (p == 0) return 0;
+  std::vector<double> a((size_t)p * p), q, l;
+  for (int m = 0; m < p; ++m)
+    for (int n = 0; n < p; ++n)
+      a[(size_t)m * p + n] = 0.5 * (c[(size_t)m * kRefDegree + n] + c[(size_t)n * kRefDegree + m]);
+  jacobi_eigh(a, p, q, l);
+  // eigenpairs in descending order (ties: the lower index first); negative eigenvalues are always dropped, then the smallest
+  // while p * sum |dropped l| <= tol: |T(x)^T (C - G G^T) T(y)| <= sum_dropped |l| (q^T T(x)) (q^T T(y)) <= p sum |l|
+  std::vector<int> ord(p);
+  for (int i = 0; i < p; ++i) ord[i] = i;
+  for (int i = 1; i < p; ++i)                             // insertion sort: stable, deterministic
+    for (int k = i; k > 0 && l[ord[k]] > l[ord[k - 1]]; --k) {
+      const int t = ord[k];
+      ord[k] = ord[k - 1];
+      ord[k - 1] = t;
+    }
+  int r = p;
+  double dropped = 0.0;
+  while (r > 0 && l[ord[r - 1]] < 0.0) dropped += fabs(l[ord[--r]]);
+  while (r > 1 && p * (dropped + l[ord[r - 1]]) <= tol) dropped += l[ord[--r]];
+  if (r < 1) return 0;
+  std::vector<double> g((size_t)p * r);
+  for (int m = 0; m < p; ++m)
+    for (int k = 0; k < r; ++k) g[(size_t)m * r + k] = q[(size_t)m * p + ord[k]] * sqrt(l[ord[k]]);
+  // the bound also covers the factorisation's own rounding: the entrywise sum of |C - G G^T| bounds |T(x)^T (C - G G^T) T(y)|
+  double resid = 0.0;
+  for (int m = 0; m < p; ++m)
+    for (int n = 0; n < p; ++n) {
+      double s = 0.0;
+      for (int k = 0; k < r; ++k) s += g[(size_t)m * r + k] * g[(size_t)n * r + k];
+      resid += fabs(c[(size_t)m * kRefDegree + n] - s);
+    }
+  const double bound = (p * dropped > resid ? p * dropped : resid) * (1.0 + 1e-12) + 1e-15;
+  *p_host = p;
+  *r_host = r;
+  if (tail_host) *tail_host = tail + bound;
+  if (G_host)
+    for (int m = 0; m < p; ++m)
+      for (int k = 0; k < r; ++k) G_host[(size_t)m * p_max + k] = g[(size_t)m * r + k];
+  return 0;
+}
+
+int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w, const double *G,
+                              int p, int r, double sqrt_scale, double *B, int64_t ldb, void *stream) {
+  if (!Z || !mid || !G || !B || N < 1 || J < 1 || J > kPrepMaxJ || ldz < J || p < 1 || p > kMaxRank || r < 1 || r > p ||
+      ldb < (int64_t)J * r || N > ((int64_t)1 << 36))
+    return RPGP_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
+#define RPGP_FEAT(PB)                                                                                                   \
+  case PB:                                                                                                              \
+    hipLaunchKernelGGL(lr_features_kernel<PB>, grid, dim3(256), 0, st, Z, (long long)N, J, ldz, mid, inv_w, G, p, r,       \
+                       sqrt_scale, B, (long long)ldb);                                                                  \
+    break;
+  switch (pad8(p)) {
+    RPGP_FEAT(8)
+    RPGP_FEAT(16)
+    RPGP_FEAT(24)
+    RPGP_FEAT(32)
+    RPGP_FEAT(40)
+    RPGP_FEAT(48)
+    RPGP_FEAT(56)
+    RPGP_FEAT(64)
+    default: return RPGP_EINVAL;
+  }
+#undef RPGP_FEAT
+  return (int)hipGetLastError();
 }
 
 }  // extern "C"

@@ -60,6 +60,21 @@ class PredictionStrategy:
             self.op = model.covar_module(x)                        # train-train operator
             self.noise = model.likelihood.noise.reshape(()).detach()
             self.r = (y - self.mean_const).reshape(-1, 1)
+            # settings.lowrank_posterior: the closed-form posterior of the explicit low-rank features where it is served
+            # (lowrank_posterior.py); no caches, preconditioner, CG or refinement are built unless a call falls back
+            self.lowrank = None
+            self.lowrank_fallback_reason = None
+            if settings.lowrank_posterior.on():
+                from .lowrank_posterior import LowrankPosterior
+                self.lowrank, self.lowrank_fallback_reason = LowrankPosterior.build(self)
+            if self.lowrank is None:
+                self._init_exact()
+
+    def _init_exact(self):
+        """Today's state of the strategy: the dense factor, or the caches, the preconditioner and the refined mean cache."""
+        model = self.model
+        x = model.train_inputs
+        with torch.no_grad():
             N = x.shape[0]
             self.dense_path = isinstance(self.op, DenseKernelOperator) or use_cholesky(N) or \
                 not settings.fast_computations.solves()
@@ -246,8 +261,10 @@ class PredictionStrategy:
 
     # ---- posterior at the training inputs in closed form -----------------------------------------------------------------
     def _train_closed_form_ready(self, like):
-        """Closed form available: the dense (Cholesky) regime, or the CG regime where the float32 factor + float64 copy of
-        the mixed-precision solve exist / fit (settings.solve_refinement on)."""
+        """Closed form available: the feature posterior, the dense (Cholesky) regime, or the CG regime where the float32
+        factor + float64 copy of the mixed-precision solve exist / fit (settings.solve_refinement on)."""
+        if self.lowrank is not None:
+            return True
         if self.dense_path:
             return True
         n = self.r.shape[0]
@@ -260,6 +277,8 @@ class PredictionStrategy:
         i.e. one more factorisation (of B, same kernel matrix with another diagonal) instead of the N x N posterior
         covariance, its N^3 products and a float64 Cholesky of it.  Replaces `mll(train_outputs, trainY)` of
         training_routines.py:567-569 for the train set."""
+        if self.lowrank is not None:
+            return self.lowrank.train_log_prob(target)
         N = self.r.shape[0]
         s2 = host_float(self.noise)
         mean = (self.model.train_targets.double().reshape(-1, 1) - s2 *
@@ -316,6 +335,8 @@ class PredictionStrategy:
         return -0.5 * (quad + logdet + N * LOG2PI)
 
     def solve(self, B):
+        if self.lowrank is not None:
+            return self.lowrank.solve(B)
         if self.dense_path:
             return torch.cholesky_solve(B, self.chol)
         khat = self.khat
@@ -380,10 +401,24 @@ class PredictionStrategy:
             self._chol64 = psd_safe_cholesky(self._dense_khat.to_dense().double())
         return self._chol64
 
+    def _lowrank_predict(self, xs, at_train=False):
+        """The feature posterior at xs, or None after building today's state for a call the features do not serve."""
+        out = self.lowrank.predict(xs, at_train=at_train)
+        if out is None and not getattr(self, "_exact_ready", False):
+            self.alpha64 = None
+            self._init_exact()
+            self._exact_ready = True
+        return out
+
     def predict(self, xs):
         model = self.model
         at_train = xs is model.train_inputs or (xs.shape == model.train_inputs.shape and
                                                 xs.data_ptr() == model.train_inputs.data_ptr())
+        if self.lowrank is not None:
+            out = self._lowrank_predict(xs, at_train)
+            if out is not None:
+                return out
+            return self._predict_exact(xs)
         with torch.no_grad():
             if at_train and self._train_closed_form_ready(xs):
                 # the posterior AT the training inputs (`evaluate_on_train`, training_routines.py:551-556): the mean is
@@ -397,6 +432,13 @@ class PredictionStrategy:
             return self._predict_general(xs)
 
     def _predict_general(self, xs):
+        if self.lowrank is not None:
+            out = self._lowrank_predict(xs)
+            if out is not None:
+                return out
+        return self._predict_exact(xs)
+
+    def _predict_exact(self, xs):
         model = self.model
         with torch.no_grad():
             cross = model.covar_module(xs, model.train_inputs)      # K(X*, X) operator

@@ -328,6 +328,43 @@ def lowrank_train_plan(prep, scale, noise):
     return cached if cached.served else None
 
 
+def lowrank_post_select(h, tol, p_max=64):
+    """(p, r, tail, G) of rpgp_lowrank_post_select (host only): G (p x r float64 numpy) with C ~= G G^T for the 1-D term
+    exp2(-h^2 (x - y)^2) on [-1, 1]^2, `tail` the bound of |T(x)^T G G^T T(y) - exp2(-h^2 (x - y)^2)|; p = r = 0: not served."""
+    import ctypes
+    import numpy as np
+    lib = _lib.load()
+    p, r, tail = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0.0)
+    G = np.zeros((p_max, p_max), dtype=np.float64)
+    _lib.check(lib.rpgp_lowrank_post_select(float(h), float(tol), int(p_max), ctypes.byref(p), ctypes.byref(r),
+                                            ctypes.byref(tail), G.ctypes.data), "rpgp_lowrank_post_select")
+    p, r = int(p.value), int(r.value)
+    return p, r, float(tail.value), G[:p, :r].copy()
+
+
+def lowrank_features(Z, mid, inv_w, G, scale, out=None):
+    """B (N x J r float64) with B[i, j r + k] = sqrt(scale) sum_m T_m((Z[i, j] - mid[j]) inv_w) G[m, k]
+    (rpgp_lowrank_features_f64): the explicit features of the truncated kernel, K_lr = B B^T."""
+    import math
+    lib = _lib.load()
+    Z = _require(Z, "Z", 2, allow64=True)
+    if Z.dtype != torch.float64:
+        raise TypeError("Z must be float64")
+    N, J = Z.shape
+    Gt = torch.as_tensor(G, dtype=torch.float64).to(Z.device).contiguous()
+    p, r = Gt.shape
+    mid_t = torch.as_tensor(mid, dtype=torch.float64).to(Z.device).reshape(-1).contiguous()
+    if mid_t.numel() != J:
+        raise ValueError("mid must have one entry per projection")
+    if out is None:
+        out = torch.empty((N, J * r), dtype=torch.float64, device=Z.device)
+    with _on(Z.device):
+        _lib.check(lib.rpgp_lowrank_features_f64(Z.data_ptr(), N, J, J, mid_t.data_ptr(), float(inv_w), Gt.data_ptr(), p, r,
+                                                 math.sqrt(float(scale)), out.data_ptr(), out.stride(0), _stream()),
+                   "rpgp_lowrank_features_f64")
+    return out
+
+
 def bilinear_grad_lowrank(plan, L, R, scale, j0=0, j1=None):
     """(gZ [N x J], gscale [scalar tensor]) of bilinear_grad on the plan's Z, from the low-rank form (rpgp_bilinear_grad_lowrank).
     The columns outside [j0, j1) are zero."""

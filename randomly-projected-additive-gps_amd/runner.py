@@ -248,6 +248,8 @@ def build_parser():
                    help="(rpgp) never materialise K: every CG iteration runs the fused recompute-in-kernel MVM")
     p.add_argument("--lowrank_kernel", action="store_true",
                    help="(rpgp) train and solve the exact kernel through its Chebyshev low-rank form where its ranks fit")
+    p.add_argument("--lowrank_posterior", action="store_true",
+                   help="(rpgp) predict in closed form from the explicit features of the Chebyshev low-rank kernel where served")
     return p
 
 
@@ -399,7 +401,8 @@ def main(argv=None, rank_entry=None):
                 settings.beta_features.checkpoint_kernel(args.checkpoint_kernel), \
                 settings.skip_logdet_forward(args.skip_log_det_forward), \
                 settings.memory_efficient(args.memory_efficient), settings.cache_kernel(args.cache_kernel), \
-                settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)):
+                settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)), \
+                settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)):
             if args.ablation:
                 if args.k is not None:
                     abl_vars = args.k

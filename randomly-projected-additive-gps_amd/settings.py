@@ -137,6 +137,11 @@ native_sharded_cg = _setting("native_sharded_cg", True, flag=True)
 # p, q <= 64 is solved through RPGP_OP_LOWRANK (no packed / dense cache) and differentiated by rpgp_bilinear_grad_lowrank — both
 # or neither, decided once per operator.  Off: the exact sweep.  RPGP_LOWRANK=0 and RPGP_FACT_ASM keep the sweep either way.
 lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
+# prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
+# with a float64 twin (k = 1, no grid), J <= 64, at most 4096 features in 25 % of the device memory gets its posterior mean,
+# covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
+# where it is not served: the prediction strategy as before.
+lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
 
 
 class fast_computations:
