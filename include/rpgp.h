@@ -189,6 +189,21 @@ int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const 
                               int p, int r, double sqrt_scale, double *B, int64_t ldb, void *stream);
 
 /*
+ * The adjoint of rpgp_lowrank_features_f64 (the closed-form marginal likelihood's derivative through the features).  With
+ * W = ca alpha v^T + cy Y (N x J r; formed row by row, never stored) and x_ij = (Z[i ldz + j] - mid[j]) * inv_w:
+ *   rpgp_lowrank_features_grad_f64: gZ[i ldg + j] = sqrt_scale * inv_w * sum_{m < p} T_m(x_ij) sum_{k < r} Gd[m r + k] W[i, j r + k]
+ *     Gd (p x r, compact row-major) are the derivative coefficients of the features' G: sum_m T'_m(x) G[m r + k] =
+ *     sum_m T_m(x) Gd[m r + k] (the host's Chebyshev derivative recurrence), so gZ = dL/dZ for dL/dB = W.  Z (N x ldz), mid (J),
+ *     Y (N x ldy), alpha (N), v (J r) and gZ are float64 device arrays.  Float64 throughout, in a fixed order, without atomics:
+ *     each (i, j) is written once and repeated calls are bit-identical; the columns [J, ldg) of gZ are not written.
+ *     Limits: N >= 1, 1 <= J <= 64, ldz >= J, 1 <= r <= p <= 64, ldy >= J r, ldg >= J.
+ */
+int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w,
+                                   const double *Gd, int p, int r, double sqrt_scale, const double *Y, int64_t ldy,
+                                   const double *alpha, const double *v, double ca, double cy, double *gZ, int64_t ldg,
+                                   void *stream);
+
+/*
  * Rectangular fused MVM:  out = scale * sum_j K_j(Z1,Z2) @ V      (Z1: M x ., Z2: N x ., V: N x T, out: M x T)
  * Replaces K(X*,X) @ alpha and K(X,X*) blocks of the prediction strategy driven from training_routines.py:551-575.
  */

@@ -19,6 +19,7 @@ class HipBackend:
     bilinear_grad_lowrank = staticmethod(ops.bilinear_grad_lowrank)
     lowrank_post_select = staticmethod(ops.lowrank_post_select)
     lowrank_features = staticmethod(ops.lowrank_features)
+    lowrank_features_grad = staticmethod(ops.lowrank_features_grad)
     mvm_rect = staticmethod(ops.mvm_rect)
     dense = staticmethod(ops.dense)
     bilinear_grad = staticmethod(ops.bilinear_grad)

@@ -618,6 +618,84 @@ __global__ __launch_bounds__(256) void lr_features_kernel(const double *__restri
   }
 }
 
+// The adjoint of lr_features_kernel (rpgp_lowrank_features_grad_f64): with W = ca alpha v^T + cy Y (N x J r, never stored),
+//   gZ[i ldg + j] = fac * sum_{k < r} (sum_{m < p} T_m(x_ij) Gd[m r + k]) W[i, j r + k],   fac = sqrt_scale inv_w,
+// Gd the derivative coefficients of G (sum_m T'_m G[m, k] = sum_m T_m Gd[m, k]).  The same tiles as lr_features_kernel: Gd in
+// LDS, the (16 x PB) Chebyshev tile of a wave's 16 rows in registers, v_mfma_f64_16x16x4_f64 per column tile of 16.  Each
+// product tile (lane: col l & 15, rows (l >> 4) + 4 i) is multiplied element-wise by W read as 4 rows x 16 consecutive doubles
+// of Y, summed over the column tiles in the lane, then over the 16 lanes of a row by xor-shuffles 8, 4, 2, 1 (a fixed order);
+// lane l & 15 == 0 writes each (i, j) once.  grid (ceil(N / 64))
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_grad_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
+                                                               const double *__restrict__ mid, double inv_w,
+                                                               const double *__restrict__ Gd, int p, int r, double fac,
+                                                               const double *__restrict__ Y, long long ldy,
+                                                               const double *__restrict__ alpha, const double *__restrict__ v,
+                                                               double ca, double cy, double *__restrict__ gZ, long long ldg) {
+  __shared__ double gs[PB * kFeatLd];
+  for (int e = threadIdx.x; e < PB * 64; e += 256) {
+    const int m = e >> 6, k = e & 63;
+    gs[m * kFeatLd + k] = (m < p && k < r) ? Gd[m * r + k] : 0.0;
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c16 = lane & 15, kq = lane >> 4;
+  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
+  const long long row = rbase + c16;
+  const bool ok = row < N;
+  const int nct = (r + 15) >> 4;
+  double al[4];                                           // ca alpha of the lane's output rows kq + 4 i
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long long ro = rbase + kq + 4 * i;
+    al[i] = ro < N ? ca * alpha[ro] : 0.0;
+  }
+  for (int j = 0; j < J; ++j) {
+    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0, x2 = 2.0 * x;
+    double a[PB / 4];
+    double tm2 = 1.0, tm1 = x;
+    a[0] = kq == 0 ? 1.0 : (kq == 1 ? x : 0.0);
+#pragma unroll
+    for (int m = 2; m < PB; ++m) {                        // T_m = 2x T_{m-1} - T_{m-2}; lane keeps m = 4s + kq
+      const double tm = __builtin_fma(x2, tm1, -tm2);
+      if ((m & 3) == kq) a[m >> 2] = tm;
+      tm2 = tm1;
+      tm1 = tm;
+    }
+    double part[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int ct = 0; ct < nct; ++ct) {
+      double4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < PB / 4; ++s)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gs[(4 * s + kq) * kFeatLd + ct * 16 + c16], acc, 0, 0, 0);
+      const int col = ct * 16 + c16;
+      if (col < r) {
+        const long long f = (long long)j * r + col;
+        const double vc = v[f];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long long ro = rbase + kq + 4 * i;
+          if (ro < N) part[i] = __builtin_fma(acc[i], __builtin_fma(cy, Y[ro * ldy + f], al[i] * vc), part[i]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      part[i] += __shfl_xor(part[i], 8);
+      part[i] += __shfl_xor(part[i], 4);
+      part[i] += __shfl_xor(part[i], 2);
+      part[i] += __shfl_xor(part[i], 1);
+    }
+    if (c16 == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const long long ro = rbase + kq + 4 * i;
+        if (ro < N) gZ[ro * ldg + j] = fac * part[i];
+      }
+    }
+  }
+}
+
 // the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
 int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes, int *p_host,
                 void **handle_host, void *stream) {
@@ -892,6 +970,36 @@ int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const 
     default: return RPGP_EINVAL;
   }
 #undef RPGP_FEAT
+  return (int)hipGetLastError();
+}
+
+int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w,
+                                   const double *Gd, int p, int r, double sqrt_scale, const double *Y, int64_t ldy,
+                                   const double *alpha, const double *v, double ca, double cy, double *gZ, int64_t ldg,
+                                   void *stream) {
+  if (!Z || !mid || !Gd || !Y || !alpha || !v || !gZ || N < 1 || J < 1 || J > kPrepMaxJ || ldz < J || p < 1 ||
+      p > kMaxRank || r < 1 || r > p || ldy < (int64_t)J * r || ldg < J || N > ((int64_t)1 << 36))
+    return RPGP_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
+  const double fac = sqrt_scale * inv_w;
+#define RPGP_FEAT_GRAD(PB)                                                                                              \
+  case PB:                                                                                                              \
+    hipLaunchKernelGGL(lr_features_grad_kernel<PB>, grid, dim3(256), 0, st, Z, (long long)N, J, ldz, mid, inv_w, Gd, p,   \
+                       r, fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);                                \
+    break;
+  switch (pad8(p)) {
+    RPGP_FEAT_GRAD(8)
+    RPGP_FEAT_GRAD(16)
+    RPGP_FEAT_GRAD(24)
+    RPGP_FEAT_GRAD(32)
+    RPGP_FEAT_GRAD(40)
+    RPGP_FEAT_GRAD(48)
+    RPGP_FEAT_GRAD(56)
+    RPGP_FEAT_GRAD(64)
+    default: return RPGP_EINVAL;
+  }
+#undef RPGP_FEAT_GRAD
   return (int)hipGetLastError();
 }
 

@@ -108,7 +108,12 @@ class _FusedMLL(torch.autograd.Function):
         ctx.sign = sign
         ctx.eager = None
         ctx.want_eager = bool(eager)
-        if _native_step_ok(model, target, raw_ls):
+        prepared = None
+        if settings.lowrank_mll.on():
+            # the closed-form features mode is decided before the step kernels: where it serves the operator, the step is
+            # InvQuadLogDet's "features" mode below (the same numbers as the generic objective); where not, as if it were off
+            prepared = _FusedMLL._prepare(raw_ls, raw_os, raw_noise, model, likelihood)
+        if (prepared is None or not prepared[-1].lowrank_mll_served) and _native_step_ok(model, target, raw_ls):
             done = _FusedMLL._forward_native(ctx, raw_ls, raw_os, raw_noise, mean_c, model, likelihood, target)
             if done is not None:
                 return done
@@ -118,6 +123,29 @@ class _FusedMLL(torch.autograd.Function):
         bk = pk.base_kernel
         X = model.train_inputs
         n = X.shape[0]
+        if prepared is None:
+            prepared = _FusedMLL._prepare(raw_ls, raw_os, raw_noise, model, likelihood)
+        ls, os_, noise, noise_f, P, col, Z, op = prepared
+        with torch.no_grad():
+            r = target - mean_c
+            st = _Ctx()
+            inv_quad, logdet = InvQuadLogDet.forward(st, Z, os_, noise, r, op, None)
+            lp, dlp = _prior(likelihood, noise_f)
+            # mll = (-0.5 (inv_quad + logdet + n log 2 pi) + log p(sigma^2)) / n      (models.ExactMarginalLogLikelihood)
+            value = (inv_quad + logdet) * (sign * -0.5 / n) + (sign * (-0.5 * n * LOG2PI + lp) / n)
+        ctx.st, ctx.n, ctx.dlp, ctx.prescale = st, n, dlp, pk.prescale
+        ctx.zfac = bk.input_scale_factor()            # the operator acts on zfac * Z (inner lengthscale of the base kernel)
+        ctx.X, ctx.P, ctx.ls, ctx.col = X, P, ls, col
+        ctx.save_for_backward(raw_ls, raw_os, raw_noise)
+        return value.to(raw_ls.dtype)
+
+    @staticmethod
+    def _prepare(raw_ls, raw_os, raw_noise, model, likelihood):
+        """(ls, outputscale, noise, its host value, P, the lengthscale column, Z, operator) of the generic forward pass; with
+        settings.lowrank_mll on, the operator has decided whether the features mode serves it."""
+        pk = model.covar_module.base_kernel
+        bk = pk.base_kernel
+        X = model.train_inputs
         with torch.no_grad():
             ls = F.softplus(raw_ls).reshape(-1)
             os_ = F.softplus(raw_os).reshape(())
@@ -130,17 +158,9 @@ class _FusedMLL(torch.autograd.Function):
             Z = _backend.get_backend().project(X.contiguous(), Peff)
             op = bk.operator(Z, None, outputscale=os_, shard=None)
             op._noise_host = noise_f
-            r = target - mean_c
-            st = _Ctx()
-            inv_quad, logdet = InvQuadLogDet.forward(st, Z, os_, noise, r, op, None)
-            lp, dlp = _prior(likelihood, noise_f)
-            # mll = (-0.5 (inv_quad + logdet + n log 2 pi) + log p(sigma^2)) / n      (models.ExactMarginalLogLikelihood)
-            value = (inv_quad + logdet) * (sign * -0.5 / n) + (sign * (-0.5 * n * LOG2PI + lp) / n)
-        ctx.st, ctx.n, ctx.dlp, ctx.prescale = st, n, dlp, pk.prescale
-        ctx.zfac = bk.input_scale_factor()            # the operator acts on zfac * Z (inner lengthscale of the base kernel)
-        ctx.X, ctx.P, ctx.ls, ctx.col = X, P, ls, col
-        ctx.save_for_backward(raw_ls, raw_os, raw_noise)
-        return value.to(raw_ls.dtype)
+            if settings.lowrank_mll.on():
+                op.lowrank_mll_form(noise_f)
+        return ls, os_, noise, noise_f, P, col, Z, op
 
     @staticmethod
     def _forward_native(ctx, raw_ls, raw_os, raw_noise, mean_c, model, likelihood, target):
@@ -324,6 +344,8 @@ def value_and_grad(model, likelihood, target, negate=True):
     params = (pk.raw_lengthscale, model.covar_module.raw_outputscale, likelihood.raw_noise, model.mean_module.constant)
     if not all(p.requires_grad and p.is_leaf for p in params) or not _native_step_ok(model, target, params[0]):
         return None
+    if settings.lowrank_mll.on():
+        return None                  # (the features mode is decided inside the node: `evaluate` and backward() take the step)
     ctx = _Ctx()
     ctx.sign = -1.0 if negate else 1.0
     ctx.eager = None

@@ -1,6 +1,7 @@
 """inv_quad / log-det of Khat = K + sigma^2 I with gradients.
 
-Two regimes, switched like GPyTorch does (Appendix B.1):
+Two regimes, switched like GPyTorch does (Appendix B.1), and a third where settings.lowrank_mll serves the operator (it then
+takes precedence over both: lowrank_mll.py, the closed form of the truncated Chebyshev low-rank kernel's features):
   * N <= settings.max_cholesky_size or fast_computations(log_prob=False): dense Cholesky of rpgp_dense(K);
     backward through the explicit-weight HIP derivative kernel (rpgp_bilinear_grad_dense);
   * otherwise: preconditioned mBCG on [probes | y - c] (T = num_trace_samples + 1 = 11), SLQ log-det from the
@@ -115,6 +116,9 @@ class InvQuadLogDet(torch.autograd.Function):
         r = rhs.detach().reshape(N, 1)
         ctx.op = op
         ctx.N = N
+        if settings.lowrank_mll.on() and hasattr(op, "lowrank_mll_form") and op.lowrank_mll_form(noise_f) is not None:
+            from . import lowrank_mll
+            return lowrank_mll.forward(ctx, Z, r, op, op.lowrank_mll_form())
         if use_cholesky(N):
             Kd = khat.to_dense()
             Lc = psd_safe_cholesky(Kd)
@@ -184,6 +188,9 @@ class InvQuadLogDet(torch.autograd.Function):
                 gr = (2.0 * g_inv_quad * alpha).reshape(-1)
         elif ctx.mode == "cg_rows":
             return _row_sharded_backward(ctx, g_inv_quad, g_logdet)
+        elif ctx.mode == "features":
+            from . import lowrank_mll
+            gZ, gs, gn, gr = lowrank_mll.backward(ctx, g_inv_quad, g_logdet)
         else:
             probe_solves, probes, alpha = ctx.saved_tensors
             p = ctx.num_probes

@@ -180,7 +180,9 @@ class MemoryEfficientGamKernel(AdditiveStructureRBFKernel):
 
     def operator(self, Z1, Z2, outputscale=None, shard=None):
         ls = self.lengthscale
-        return super().operator(Z1 / ls, None if Z2 is None else Z2 / ls, outputscale=outputscale, shard=shard)
+        op = super().operator(Z1 / ls, None if Z2 is None else Z2 / ls, outputscale=outputscale, shard=shard)
+        op.memory_efficient = True          # (settings.lowrank_mll does not serve it)
+        return op
 
     def forward(self, x1, x2, outputscale=None, shard=None, **params):
         same = x2 is None or x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())

@@ -105,6 +105,7 @@ class AdditiveRPOperator(LinearOperator):
         self._scale_value = None
         self._prep = None          # rpgp_prepare tables for the factorised fast path (built on first use)
         self._lowrank = None       # settings.lowrank_kernel: None undecided, False the sweep, else the ops.LowrankTrainPlan
+        self._lowrank_mll = None   # settings.lowrank_mll: None undecided, else (lowrank_mll.FeatureForm or None, reason)
 
     @property
     def _scale(self):
@@ -201,6 +202,29 @@ class AdditiveRPOperator(LinearOperator):
                 if plan is not None:
                     self._lowrank = plan
         return self._lowrank or None
+
+    def lowrank_mll_form(self, noise=None):
+        """The explicit features (lowrank_mll.FeatureForm) on which settings.lowrank_mll evaluates this operator's marginal
+        likelihood in closed form, or None when that mode does not serve it (the reason: `lowrank_mll_reason`).  Decided ONCE
+        per operator (= per hyper-parameter step), from the noise (default: the host value the marginal likelihood recorded)."""
+        if getattr(self, "_lowrank_mll", None) is None:
+            from . import lowrank_mll
+            if noise is None:
+                noise = getattr(self, "_noise_host", None)
+            self._lowrank_mll = lowrank_mll.decide(self, None if noise is None else float(noise))
+        return self._lowrank_mll[0]
+
+    @property
+    def lowrank_mll_served(self):
+        """Whether the closed-form features mode serves this operator (False while undecided)."""
+        d = getattr(self, "_lowrank_mll", None)
+        return bool(d and d[0] is not None)
+
+    @property
+    def lowrank_mll_reason(self):
+        """Why the features mode does not serve this operator (None when it does or while undecided)."""
+        d = getattr(self, "_lowrank_mll", None)
+        return d[1] if d else None
 
     @property
     def lowrank_served(self):

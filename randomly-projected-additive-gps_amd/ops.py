@@ -365,6 +365,61 @@ def lowrank_features(Z, mid, inv_w, G, scale, out=None):
     return out
 
 
+def chebyshev_derivative(G):
+    """Gd (p x r float64 numpy) with sum_m T'_m(x) G[m, k] = sum_m T_m(x) Gd[m, k]: the Chebyshev derivative recurrence
+    d_m = d_{m+2} + 2 (m + 1) c_{m+1} (d_p = d_{p+1} = 0), halved at m = 0.  Row p - 1 is zero."""
+    import numpy as np
+    G = np.asarray(G, dtype=np.float64)
+    p = G.shape[0]
+    D = np.zeros((p + 2,) + G.shape[1:], dtype=np.float64)
+    for m in range(p - 2, -1, -1):
+        D[m] = D[m + 2] + (2.0 * (m + 1)) * G[m + 1]
+    D[0] *= 0.5
+    return D[:p].copy()
+
+
+def lowrank_features_grad(Z, mid, inv_w, G, scale, Y, alpha, v, ca, cy, out=None):
+    """gZ (N x J float64) = dL/dZ for dL/dB = W = ca alpha v^T + cy Y through B = lowrank_features(Z, mid, inv_w, G, scale)
+    (rpgp_lowrank_features_grad_f64, with the derivative coefficients of G formed here).  `out`: an N x J float64 view with unit
+    column stride and any row stride (its columns beyond J are not touched).  ValueError outside J <= 64, r <= p <= 64."""
+    import math
+    lib = _lib.load()
+    Z = _require(Z, "Z", 2, allow64=True)
+    if Z.dtype != torch.float64:
+        raise TypeError("Z must be float64")
+    N, J = Z.shape
+    Gd = chebyshev_derivative(torch.as_tensor(G, dtype=torch.float64).cpu().numpy())
+    if Gd.ndim != 2:
+        raise ValueError("G must be p x r")
+    p, r = Gd.shape
+    if N < 1 or not 1 <= J <= 64 or not 1 <= r <= p <= 64:
+        raise ValueError("lowrank_features_grad: N = %d, J = %d, p = %d, r = %d outside N >= 1, J <= 64, r <= p <= 64"
+                         % (N, J, p, r))
+    dev = Z.device
+    Gd_t = torch.from_numpy(Gd).to(dev).contiguous()
+    mid_t = torch.as_tensor(mid, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+    if mid_t.numel() != J:
+        raise ValueError("mid must have one entry per projection")
+    if Y.dtype != torch.float64 or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] < J * r or Y.stride(1) != 1 or Y.device != dev:
+        raise ValueError("Y must be an N x (>= J r) float64 matrix on Z's device with unit column stride")
+    alpha_t = alpha.reshape(-1)
+    v_t = v.reshape(-1)
+    if alpha_t.dtype != torch.float64 or alpha_t.numel() != N or v_t.dtype != torch.float64 or v_t.numel() != J * r:
+        raise ValueError("alpha (N) and v (J r) must be float64")
+    alpha_t, v_t = alpha_t.contiguous(), v_t.contiguous()
+    if out is None:
+        out = torch.empty((N, J), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (N, J) or out.stride(1) != 1 or out.device != dev:
+        raise ValueError("out must be an N x J float64 view with unit column stride")
+    with _on(dev):
+        _lib.check(lib.rpgp_lowrank_features_grad_f64(Z.data_ptr(), N, J, J, mid_t.data_ptr(), float(inv_w), Gd_t.data_ptr(),
+                                                      p, r, math.sqrt(float(scale)), Y.data_ptr(), Y.stride(0),
+                                                      alpha_t.data_ptr(), v_t.data_ptr(), float(ca), float(cy),
+                                                      out.data_ptr(), out.stride(0), _stream()),
+                   "rpgp_lowrank_features_grad_f64")
+    return out
+
+
 def bilinear_grad_lowrank(plan, L, R, scale, j0=0, j1=None):
     """(gZ [N x J], gscale [scalar tensor]) of bilinear_grad on the plan's Z, from the low-rank form (rpgp_bilinear_grad_lowrank).
     The columns outside [j0, j1) are zero."""

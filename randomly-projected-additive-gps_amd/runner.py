@@ -250,6 +250,8 @@ def build_parser():
                    help="(rpgp) train and solve the exact kernel through its Chebyshev low-rank form where its ranks fit")
     p.add_argument("--lowrank_posterior", action="store_true",
                    help="(rpgp) predict in closed form from the explicit features of the Chebyshev low-rank kernel where served")
+    p.add_argument("--lowrank_mll", action="store_true",
+                   help="(rpgp) train on the closed-form marginal likelihood of the Chebyshev low-rank features where served")
     return p
 
 
@@ -402,7 +404,8 @@ def main(argv=None, rank_entry=None):
                 settings.skip_logdet_forward(args.skip_log_det_forward), \
                 settings.memory_efficient(args.memory_efficient), settings.cache_kernel(args.cache_kernel), \
                 settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)), \
-                settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)):
+                settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)), \
+                settings.lowrank_mll(getattr(args, "lowrank_mll", False)):
             if args.ablation:
                 if args.k is not None:
                     abl_vars = args.k

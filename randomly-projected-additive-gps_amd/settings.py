@@ -142,6 +142,14 @@ lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
 # covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
 # where it is not served: the prediction strategy as before.
 lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
+# training on the exact marginal likelihood of the same truncated kernel in closed form (lowrank_mll.py): value and full
+# gradient from the explicit features B (K_lr = B B^T) through F x F factorisations in float64: no probes, no CG, no SLQ, the
+# same deterministic function for the value and the gradient (what an L-BFGS line search needs).  Decided once per operator
+# (AdditiveRPOperator.lowrank_mll_form): an unsharded plain additive-RP RBF operator (k = 1, no grid, not memory-efficient),
+# J <= 64, Chebyshev rank p <= 64 at lowrank_posterior's tail tolerance, F < N, F <= 4096, B and B M^-1 in 25 % of the device
+# memory.  Where served it takes precedence over lowrank_kernel and over the Cholesky regime (use_cholesky); where not, the
+# step runs exactly as with the setting off (lowrank_kernel then applies as before).
+lowrank_mll = _setting("lowrank_mll", False, flag=True)
 
 
 class fast_computations:
