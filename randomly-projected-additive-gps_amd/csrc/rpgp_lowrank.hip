@@ -172,30 +172,55 @@ __global__ __launch_bounds__(256) void lr_coords_kernel(const float2v *__restric
   }
 }
 
+// One level of a transposed wave reduction: a + b after the exchange is, in the lanes that keep `a`, the sum of a over the lane
+// and its partner, in the other lanes that of b.  HALF = 32: lanes 0-31 keep a, partner l ^ 32 (v_permlane32_swap: lanes 32-63
+// of the first operand change places with lanes 0-31 of the second); HALF = 16: the even rows of 16 keep a, partner l ^ 16
+// (v_permlane16_swap: odd rows of the first with even rows of the second).  3 instructions for two values where two butterflies
+// take 6, and half as many values are live afterwards.
+template <int HALF> __device__ __forceinline__ double swap_add(double a, double b) {
+  const unsigned long long ab = __builtin_bit_cast(unsigned long long, a), bb = __builtin_bit_cast(unsigned long long, b);
+  unsigned alo, blo, ahi, bhi;
+  if constexpr (HALF == 32) {
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)ab, (unsigned)bb, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(ab >> 32), (unsigned)(bb >> 32), false, false);
+    alo = lo[0], blo = lo[1], ahi = hi[0], bhi = hi[1];
+  } else {
+    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)ab, (unsigned)bb, false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(ab >> 32), (unsigned)(bb >> 32), false, false);
+    alo = lo[0], blo = lo[1], ahi = hi[0], bhi = hi[1];
+  }
+  return __builtin_bit_cast(double, ((unsigned long long)ahi << 32) | alo) +
+         __builtin_bit_cast(double, ((unsigned long long)bhi << 32) | blo);
+}
+
 // (a) block partials part[b][jj][t][0..PB) = sum over the block's rows of T_m(x_ij) v_it.  grid (row blocks, jn, T)
 // The sums are float64 (T_m v exact, then added): W is a sum of N terms of both signs that C turns into a much smaller
 // product — in float32 its rounding alone is ~1e-6 of the result (measured in an emulation at N = 20 011), in float64 ~3e-8.
+// The 64 lanes' PB accumulators are summed transposed: two exchange levels (lane ^ 32, lane ^ 16) halve the live values each,
+// leaving PB / 4 per lane (row r of 16 lanes holds m = r PB / 4 + i), which four DPP steps sum inside the row: ~5 PB
+// instructions per wave where PB butterflies took ~23 PB.  The order of the additions is a function of PB alone.
+// PB = 40: 106 VGPR, PB = 48: 121, PB = 64: 154; no scratch.
 template <int PB>
 __global__ __launch_bounds__(256) void lr_project_kernel(const float *__restrict__ xt, const float *__restrict__ V,
                                                          double *__restrict__ part, int N, int T, int j0, int jn) {
-  __shared__ double red[4][PB];
+  __shared__ double red[4 * PB];
   const int b = blockIdx.x, jj = blockIdx.y, t = blockIdx.z;
   const float *x = xt + (size_t)(j0 + jj) * N;
   const int r0 = b * kProjRows + (int)threadIdx.x;
   float xv[kProjRowsPerThread], vv[kProjRowsPerThread];
 #pragma unroll
-  for (int u = 0; u < kProjRowsPerThread; ++u) {          // every load requested before the first use
-    const int i = r0 + u * 256;
-    const bool ok = i < N;
-    xv[u] = ok ? x[i] : 0.f;
-    vv[u] = ok ? V[(size_t)i * T + t] : 0.f;
+  for (int u = 0; u < kProjRowsPerThread; ++u) {          // every load requested before the first use: no branch around a
+    const int i = r0 + u * 256, ic = i < N ? i : N - 1;   // load (a row past N reads row N - 1 and counts with v = 0)
+    xv[u] = x[ic];
+    vv[u] = V[(size_t)ic * T + t];
   }
+  __builtin_amdgcn_sched_barrier(0);                      // (the scheduler would sink each load to one row ahead of its use)
   double acc[PB];
 #pragma unroll
   for (int m = 0; m < PB; ++m) acc[m] = 0.0;
 #pragma unroll
   for (int u = 0; u < kProjRowsPerThread; ++u) {
-    const float xi = xv[u], v = vv[u], x2 = 2.f * xi;
+    const float xi = xv[u], v = r0 + u * 256 < N ? vv[u] : 0.f, x2 = 2.f * xi;
     float tm2 = 1.f, tm1 = xi;
     acc[0] += (double)v;
     acc[1] = __builtin_fma((double)xi, (double)v, acc[1]);
@@ -207,16 +232,23 @@ __global__ __launch_bounds__(256) void lr_project_kernel(const float *__restrict
       tm1 = tm;
     }
   }
+  constexpr int QB = PB / 4;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
-  for (int m = 0; m < PB; ++m) {
-    const double s = wave_sum(acc[m]);
-    if (lane == 0) red[w][m] = s;
+  for (int i = 0; i < PB / 2; ++i) acc[i] = swap_add<32>(acc[i], acc[i + PB / 2]);
+#pragma unroll
+  for (int i = 0; i < QB; ++i) {
+    double s = swap_add<16>(acc[i], acc[i + QB]);
+    s += dpp_d<0xb1>(s);    // quad_perm [1,0,3,2]
+    s += dpp_d<0x4e>(s);    // quad_perm [2,3,0,1]
+    s += dpp_d<0x141>(s);   // row_half_mirror
+    s += dpp_d<0x140>(s);   // row_mirror
+    if ((lane & 15) == i) red[w * PB + QB * (lane >> 4) + i] = s;
   }
   __syncthreads();
   if ((int)threadIdx.x < PB) {
     const int m = threadIdx.x;
-    part[(((size_t)b * jn + jj) * T + t) * PB + m] = (red[0][m] + red[1][m]) + (red[2][m] + red[3][m]);
+    part[(((size_t)b * jn + jj) * T + t) * PB + m] = (red[m] + red[PB + m]) + (red[2 * PB + m] + red[3 * PB + m]);
   }
 }
 
