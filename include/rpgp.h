@@ -174,15 +174,15 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
  * that every 1-D term is exp2(-h^2 (x - y)^2) ~= (G^T T(x))^T (G^T T(y)) and the kernel is K_lr = B B^T with
  * B = sqrt(scale) [T(x_1) G | ... | T(x_J) G]  (N x J r).
  *   rpgp_lowrank_post_select (host only, no device): p = the rank of rpgp_lowrank_select at the per-entry tolerance `tol` (p_max
- *     <= 128), C = the p x p coefficients, factored by a symmetric Jacobi eigensolver in double; the smallest eigenpairs (every
- *     negative one first) are dropped while p * sum |dropped eigenvalues| <= tol.  G = Q_r Lambda_r^1/2 goes row-major into
+ *     <= 128), C = the p x p coefficients, factored by a symmetric eigensolver in double (cyclic Jacobi for p <= 64, Householder
+ *     tridiagonalisation with implicit QL above); the smallest eigenpairs (every negative one first) are dropped while p * sum |dropped eigenvalues| <= tol.  G = Q_r Lambda_r^1/2 goes row-major into
  *     `G_host` (optional, p_max x p_max, row m at m * p_max); *tail_host (optional) = the selection's tail + the dropped bound
  *     (max of p * sum |dropped|, sum_mn |C - G G^T|_mn): it bounds |T(x)^T G G^T T(y) - exp2(-h^2 (x - y)^2)| on [-1, 1]^2.
  *     *p_host = *r_host = 0: not served (h not finite, not resolved by the reference degree, or p > p_max).  Deterministic.
  *   rpgp_lowrank_features_f64: B[i ldb + j r + k] = sqrt_scale * sum_{m < p} T_m(x_ij) G[m r + k] with
  *     x_ij = (Z[i ldz + j] - mid[j]) * inv_w; Z (N x ldz), mid (J), G (p x r, compact row-major) and B are float64 device
  *     arrays.  The recurrence and the products run in float64 in a fixed order (repeated calls are bit-identical); the
- *     columns [J r, ldb) of B are not written.  Limits: N >= 1, 1 <= J <= 64, ldz >= J, 1 <= r <= p <= 64, ldb >= J r.
+ *     columns [J r, ldb) of B are not written.  Limits: N >= 1, 1 <= J <= 64, ldz >= J, 1 <= r <= p <= 128, ldb >= J r.
  */
 int rpgp_lowrank_post_select(double h, double tol, int p_max, int *p_host, int *r_host, double *tail_host, double *G_host);
 int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w, const double *G,
@@ -196,7 +196,7 @@ int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const 
  *     sum_m T_m(x) Gd[m r + k] (the host's Chebyshev derivative recurrence), so gZ = dL/dZ for dL/dB = W.  Z (N x ldz), mid (J),
  *     Y (N x ldy), alpha (N), v (J r) and gZ are float64 device arrays.  Float64 throughout, in a fixed order, without atomics:
  *     each (i, j) is written once and repeated calls are bit-identical; the columns [J, ldg) of gZ are not written.
- *     Limits: N >= 1, 1 <= J <= 64, ldz >= J, 1 <= r <= p <= 64, ldy >= J r, ldg >= J.
+ *     Limits: N >= 1, 1 <= J <= 64, ldz >= J, 1 <= r <= p <= 128, ldy >= J r, ldg >= J.
  */
 int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w,
                                    const double *Gd, int p, int r, double sqrt_scale, const double *Y, int64_t ldy,

@@ -594,6 +594,137 @@ void jacobi_eigh(std::vector<double> &a, int p, std::vector<double> &q, std::vec
   for (int i = 0; i < p; ++i) l[i] = a[(size_t)i * p + i];
 }
 
+// The same decomposition for p > 64, where Jacobi's O(p^3) sweeps with strided column updates take 37 ms (p = 113) to 142 ms
+// (p = 128) on the host: Householder reduction to tridiagonal form, then the implicit QL iteration with the rotations
+// accumulated into q (the textbook tred2 / tql2 pair).  Deterministic: no pivoting, a fixed order.  a: p x p row-major
+// (read only); q: eigenvectors as columns; l: eigenvalues (ascending up to ties).  The caller's tail bound is taken from
+// C - G G^T itself, so it covers this solver's rounding as it covers Jacobi's.
+void tridiagonal_ql_eigh(const std::vector<double> &a, int p, std::vector<double> &q, std::vector<double> &l) {
+  q = a;
+  l.assign(p, 0.0);
+  std::vector<double> e(p, 0.0);
+  double *d = l.data();
+  auto V = [&](int i, int j) -> double & { return q[(size_t)i * p + j]; };
+  for (int j = 0; j < p; ++j) d[j] = V(p - 1, j);
+  for (int i = p - 1; i > 0; --i) {                       // Householder reduction of row i
+    double scale = 0.0, h = 0.0;
+    for (int k = 0; k < i; ++k) scale += fabs(d[k]);
+    if (scale == 0.0) {
+      e[i] = d[i - 1];
+      for (int j = 0; j < i; ++j) {
+        d[j] = V(i - 1, j);
+        V(i, j) = 0.0;
+        V(j, i) = 0.0;
+      }
+    } else {
+      for (int k = 0; k < i; ++k) {
+        d[k] /= scale;
+        h += d[k] * d[k];
+      }
+      double f = d[i - 1], g = sqrt(h);
+      if (f > 0.0) g = -g;
+      e[i] = scale * g;
+      h -= f * g;
+      d[i - 1] = f - g;
+      for (int j = 0; j < i; ++j) e[j] = 0.0;
+      for (int j = 0; j < i; ++j) {                       // e = A u (the lower triangle only)
+        f = d[j];
+        V(j, i) = f;
+        g = e[j] + V(j, j) * f;
+        for (int k = j + 1; k < i; ++k) {
+          g += V(k, j) * d[k];
+          e[k] += V(k, j) * f;
+        }
+        e[j] = g;
+      }
+      f = 0.0;
+      for (int j = 0; j < i; ++j) {
+        e[j] /= h;
+        f += e[j] * d[j];
+      }
+      const double hh = f / (h + h);
+      for (int j = 0; j < i; ++j) e[j] -= hh * d[j];
+      for (int j = 0; j < i; ++j) {                       // A <- A - u e^T - e u^T
+        f = d[j];
+        g = e[j];
+        for (int k = j; k < i; ++k) V(k, j) -= f * e[k] + g * d[k];
+        d[j] = V(i - 1, j);
+        V(i, j) = 0.0;
+      }
+    }
+    d[i] = h;
+  }
+  for (int i = 0; i < p - 1; ++i) {                       // accumulate the reflections
+    V(p - 1, i) = V(i, i);
+    V(i, i) = 1.0;
+    const double h = d[i + 1];
+    if (h != 0.0) {
+      for (int k = 0; k <= i; ++k) d[k] = V(k, i + 1) / h;
+      for (int j = 0; j <= i; ++j) {
+        double g = 0.0;
+        for (int k = 0; k <= i; ++k) g += V(k, i + 1) * V(k, j);
+        for (int k = 0; k <= i; ++k) V(k, j) -= g * d[k];
+      }
+    }
+    for (int k = 0; k <= i; ++k) V(k, i + 1) = 0.0;
+  }
+  for (int j = 0; j < p; ++j) {
+    d[j] = V(p - 1, j);
+    V(p - 1, j) = 0.0;
+  }
+  V(p - 1, p - 1) = 1.0;
+  for (int i = 1; i < p; ++i) e[i - 1] = e[i];            // implicit QL on (d, e)
+  e[p - 1] = 0.0;
+  const double eps = 2.220446049250313e-16;
+  double f = 0.0, tst1 = 0.0;
+  for (int lo = 0; lo < p; ++lo) {
+    tst1 = fmax(tst1, fabs(d[lo]) + fabs(e[lo]));
+    int m = lo;
+    while (m < p - 1 && fabs(e[m]) > eps * tst1) ++m;
+    if (m > lo) {
+      for (int iter = 0; iter < 200; ++iter) {            // (converges in a few; the bound only ends a pathological input)
+        double g = d[lo];
+        double pp = (d[lo + 1] - g) / (2.0 * e[lo]);
+        double r = hypot(pp, 1.0);
+        if (pp < 0.0) r = -r;
+        d[lo] = e[lo] / (pp + r);
+        d[lo + 1] = e[lo] * (pp + r);
+        const double dl1 = d[lo + 1];
+        double h = g - d[lo];
+        for (int i = lo + 2; i < p; ++i) d[i] -= h;
+        f += h;
+        pp = d[m];
+        double c = 1.0, c2 = 1.0, c3 = 1.0, s = 0.0, s2 = 0.0;
+        const double el1 = e[lo + 1];
+        for (int i = m - 1; i >= lo; --i) {
+          c3 = c2;
+          c2 = c;
+          s2 = s;
+          g = c * e[i];
+          h = c * pp;
+          r = hypot(pp, e[i]);
+          e[i + 1] = s * r;
+          s = e[i] / r;
+          c = pp / r;
+          pp = c * d[i] - s * g;
+          d[i + 1] = h + s * (c * g + s * d[i]);
+          for (int k = 0; k < p; ++k) {
+            h = V(k, i + 1);
+            V(k, i + 1) = s * V(k, i) + c * h;
+            V(k, i) = c * V(k, i) - s * h;
+          }
+        }
+        pp = -s * s2 * c3 * el1 * e[lo] / dl1;
+        e[lo] = s * pp;
+        d[lo] = c * pp;
+        if (fabs(e[lo]) <= eps * tst1) break;
+      }
+    }
+    d[lo] += f;
+    e[lo] = 0.0;
+  }
+}
+
 constexpr int kFeatRows = 64;            // rows per workgroup (4 waves x 16 rows, all projections)
 constexpr int kFeatLd = 80;              // LDS row stride of G in doubles: rows 4s + kq of one read land 32 banks apart
 
@@ -726,6 +857,158 @@ __global__ __launch_bounds__(256) void lr_features_grad_kernel(const double *__r
       }
     }
   }
+}
+
+// ---- padded ranks 72 ... 128 of the two kernels above (r up to p: up to 8 column tiles) -----------------------------------
+// The same tiles, order and stores; G no longer fits the 64 KB of static LDS, so it is staged in dynamic LDS sized from the
+// column tiles in use: PB rows of wide_ld(nct) doubles.  The stride stays = 16 mod 32 doubles: ds_read_b64 serves a 32-lane
+// half per cycle, lanes 0-15 read 16 consecutive doubles (banks 0-31) of row 4s + kq and lanes 16-31 those of the next row,
+// 2 * stride = 32 mod 64 banks further on: no conflict.  LDS per workgroup: PB * wide_ld * 8 bytes, from 27 KB (PB 72, one
+// tile) to 144 KB (PB 128, eight tiles) of the CU's 160 KB, so 5 ... 1 workgroups per CU (DESIGN.md §7.5 has the table).
+// Registers (hipcc 7.2, -O3, gfx950; unified VGPRs, of which 8 are AGPRs), lr_features_wide_kernel | lr_features_grad_wide_kernel,
+// no scratch and no spill in any of them:
+//   PB  72:  80 | 116      PB  80:  84 | 120      PB  88:  88 | 124      PB  96:  92 | 128
+//   PB 104:  96 | 132      PB 112: 100 | 136      PB 120: 104 | 140      PB 128: 108 | 144
+// (the narrow PB 64 kernels: 80 | 116), so registers allow 3 waves per SIMD at worst and LDS is what bounds the occupancy.
+constexpr int kFeatMaxRank = 128;        // largest p (and r) of the feature kernels; the float32 product kernels keep kMaxRank
+
+constexpr int wide_ld(int nct) { return ((nct * 16 + 31) & ~31) + 16; }           // 48, 48, 80, 80, 112, 112, 144, 144
+constexpr size_t wide_lds_bytes(int pb, int nct) { return (size_t)pb * wide_ld(nct) * sizeof(double); }
+
+// G (p x r) -> LDS rows of `ld` doubles, zero-padded to PB x 16 nct
+template <int PB>
+__device__ __forceinline__ void stage_wide(double *gs, const double *__restrict__ G, int p, int r, int nct, int ld) {
+  const int nc = nct * 16;
+  for (int e = threadIdx.x; e < PB * nc; e += 256) {
+    const int m = e / nc, k = e - m * nc;
+    gs[m * ld + k] = (m < p && k < r) ? G[m * r + k] : 0.0;
+  }
+  __syncthreads();
+}
+
+// the lane's part of the (16 x PB) Chebyshev tile: a[s] = T_{4s + kq}(x)
+template <int PB>
+__device__ __forceinline__ void chebyshev_tile(double x, int kq, double (&a)[PB / 4]) {
+  const double x2 = 2.0 * x;
+  double tm2 = 1.0, tm1 = x;
+  a[0] = kq == 0 ? 1.0 : (kq == 1 ? x : 0.0);
+#pragma unroll
+  for (int m = 2; m < PB; ++m) {                          // T_m = 2x T_{m-1} - T_{m-2}; lane keeps m = 4s + kq
+    const double tm = __builtin_fma(x2, tm1, -tm2);
+    if ((m & 3) == kq) a[m >> 2] = tm;
+    tm2 = tm1;
+    tm1 = tm;
+  }
+}
+
+// lr_features_kernel for PB in 72 ... 128.  grid (ceil(N / 64)), dynamic LDS wide_lds_bytes(PB, ceil(r / 16))
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_wide_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
+                                                               const double *__restrict__ mid, double inv_w,
+                                                               const double *__restrict__ G, int p, int r,
+                                                               double sqrt_scale, double *__restrict__ B, long long ldb) {
+  extern __shared__ double gw[];
+  const int nct = (r + 15) >> 4, ld = wide_ld(nct);
+  stage_wide<PB>(gw, G, p, r, nct, ld);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c16 = lane & 15, kq = lane >> 4;
+  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
+  const long long row = rbase + c16;
+  const bool ok = row < N;
+  const double *gl = gw + kq * ld + c16;
+  for (int j = 0; j < J; ++j) {
+    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0;
+    double a[PB / 4];
+    chebyshev_tile<PB>(x, kq, a);
+    for (int ct = 0; ct < nct; ++ct) {
+      double4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < PB / 4; ++s)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gl[4 * s * ld + ct * 16], acc, 0, 0, 0);
+      const int col = ct * 16 + c16;
+      if (col < r) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long long ro = rbase + kq + 4 * i;
+          if (ro < N) B[ro * ldb + (long long)j * r + col] = sqrt_scale * acc[i];
+        }
+      }
+    }
+  }
+}
+
+// lr_features_grad_kernel for PB in 72 ... 128.  grid (ceil(N / 64)), dynamic LDS wide_lds_bytes(PB, ceil(r / 16))
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_grad_wide_kernel(
+    const double *__restrict__ Z, long long N, int J, int ldz, const double *__restrict__ mid, double inv_w,
+    const double *__restrict__ Gd, int p, int r, double fac, const double *__restrict__ Y, long long ldy,
+    const double *__restrict__ alpha, const double *__restrict__ v, double ca, double cy, double *__restrict__ gZ,
+    long long ldg) {
+  extern __shared__ double gw[];
+  const int nct = (r + 15) >> 4, ld = wide_ld(nct);
+  stage_wide<PB>(gw, Gd, p, r, nct, ld);
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int c16 = lane & 15, kq = lane >> 4;
+  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
+  const long long row = rbase + c16;
+  const bool ok = row < N;
+  const double *gl = gw + kq * ld + c16;
+  double al[4];                                           // ca alpha of the lane's output rows kq + 4 i
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const long long ro = rbase + kq + 4 * i;
+    al[i] = ro < N ? ca * alpha[ro] : 0.0;
+  }
+  for (int j = 0; j < J; ++j) {
+    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0;
+    double a[PB / 4];
+    chebyshev_tile<PB>(x, kq, a);
+    double part[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int ct = 0; ct < nct; ++ct) {
+      double4v acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int s = 0; s < PB / 4; ++s)
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gl[4 * s * ld + ct * 16], acc, 0, 0, 0);
+      const int col = ct * 16 + c16;
+      if (col < r) {
+        const long long f = (long long)j * r + col;
+        const double vc = v[f];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const long long ro = rbase + kq + 4 * i;
+          if (ro < N) part[i] = __builtin_fma(acc[i], __builtin_fma(cy, Y[ro * ldy + f], al[i] * vc), part[i]);
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      part[i] += __shfl_xor(part[i], 8);
+      part[i] += __shfl_xor(part[i], 4);
+      part[i] += __shfl_xor(part[i], 2);
+      part[i] += __shfl_xor(part[i], 1);
+    }
+    if (c16 == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const long long ro = rbase + kq + 4 * i;
+        if (ro < N) gZ[ro * ldg + j] = fac * part[i];
+      }
+    }
+  }
+}
+
+// launch of a wide instantiation: above 64 KB the dynamic LDS needs the function attribute (set per call: it belongs to the
+// current device's copy of the kernel)
+template <typename K, typename... A>
+int launch_wide(K kernel, int pb, int r, dim3 grid, hipStream_t st, A... args) {
+  const size_t bytes = wide_lds_bytes(pb, (r + 15) >> 4);
+  if (bytes > 65536) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)wide_lds_bytes(pb, kFeatMaxRank / 16));
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(kernel, grid, dim3(256), bytes, st, args...);
+  return (int)hipGetLastError();
 }
 
 // the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
@@ -941,7 +1224,10 @@ int rpgp_lowrank_post_select(double h, double tol, int p_max, int *p_host, int *
   for (int m = 0; m < p; ++m)
     for (int n = 0; n < p; ++n)
       a[(size_t)m * p + n] = 0.5 * (c[(size_t)m * kRefDegree + n] + c[(size_t)n * kRefDegree + m]);
-  jacobi_eigh(a, p, q, l);
+  if (p <= kMaxRank)
+    jacobi_eigh(a, p, q, l);
+  else
+    tridiagonal_ql_eigh(a, p, q, l);
   // eigenpairs in descending order (ties: the lower index first); negative eigenvalues are always dropped, then the smallest
   // while p * sum |dropped l| <= tol: |T(x)^T (C - G G^T) T(y)| <= sum_dropped |l| (q^T T(x)) (q^T T(y)) <= p sum |l|
   std::vector<int> ord(p);
@@ -980,7 +1266,7 @@ int rpgp_lowrank_post_select(double h, double tol, int p_max, int *p_host, int *
 
 int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w, const double *G,
                               int p, int r, double sqrt_scale, double *B, int64_t ldb, void *stream) {
-  if (!Z || !mid || !G || !B || N < 1 || J < 1 || J > kPrepMaxJ || ldz < J || p < 1 || p > kMaxRank || r < 1 || r > p ||
+  if (!Z || !mid || !G || !B || N < 1 || J < 1 || J > kPrepMaxJ || ldz < J || p < 1 || p > kFeatMaxRank || r < 1 || r > p ||
       ldb < (int64_t)J * r || N > ((int64_t)1 << 36))
     return RPGP_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -990,6 +1276,10 @@ int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const 
     hipLaunchKernelGGL(lr_features_kernel<PB>, grid, dim3(256), 0, st, Z, (long long)N, J, ldz, mid, inv_w, G, p, r,       \
                        sqrt_scale, B, (long long)ldb);                                                                  \
     break;
+#define RPGP_FEAT_WIDE(PB)                                                                                              \
+  case PB:                                                                                                              \
+    return launch_wide(lr_features_wide_kernel<PB>, PB, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w, G, p, r,         \
+                       sqrt_scale, B, (long long)ldb);
   switch (pad8(p)) {
     RPGP_FEAT(8)
     RPGP_FEAT(16)
@@ -999,9 +1289,18 @@ int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const 
     RPGP_FEAT(48)
     RPGP_FEAT(56)
     RPGP_FEAT(64)
+    RPGP_FEAT_WIDE(72)
+    RPGP_FEAT_WIDE(80)
+    RPGP_FEAT_WIDE(88)
+    RPGP_FEAT_WIDE(96)
+    RPGP_FEAT_WIDE(104)
+    RPGP_FEAT_WIDE(112)
+    RPGP_FEAT_WIDE(120)
+    RPGP_FEAT_WIDE(128)
     default: return RPGP_EINVAL;
   }
 #undef RPGP_FEAT
+#undef RPGP_FEAT_WIDE
   return (int)hipGetLastError();
 }
 
@@ -1010,7 +1309,7 @@ int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, c
                                    const double *alpha, const double *v, double ca, double cy, double *gZ, int64_t ldg,
                                    void *stream) {
   if (!Z || !mid || !Gd || !Y || !alpha || !v || !gZ || N < 1 || J < 1 || J > kPrepMaxJ || ldz < J || p < 1 ||
-      p > kMaxRank || r < 1 || r > p || ldy < (int64_t)J * r || ldg < J || N > ((int64_t)1 << 36))
+      p > kFeatMaxRank || r < 1 || r > p || ldy < (int64_t)J * r || ldg < J || N > ((int64_t)1 << 36))
     return RPGP_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
@@ -1020,6 +1319,10 @@ int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, c
     hipLaunchKernelGGL(lr_features_grad_kernel<PB>, grid, dim3(256), 0, st, Z, (long long)N, J, ldz, mid, inv_w, Gd, p,   \
                        r, fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);                                \
     break;
+#define RPGP_FEAT_GRAD_WIDE(PB)                                                                                         \
+  case PB:                                                                                                              \
+    return launch_wide(lr_features_grad_wide_kernel<PB>, PB, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w, Gd, p, r,   \
+                       fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);
   switch (pad8(p)) {
     RPGP_FEAT_GRAD(8)
     RPGP_FEAT_GRAD(16)
@@ -1029,9 +1332,18 @@ int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, c
     RPGP_FEAT_GRAD(48)
     RPGP_FEAT_GRAD(56)
     RPGP_FEAT_GRAD(64)
+    RPGP_FEAT_GRAD_WIDE(72)
+    RPGP_FEAT_GRAD_WIDE(80)
+    RPGP_FEAT_GRAD_WIDE(88)
+    RPGP_FEAT_GRAD_WIDE(96)
+    RPGP_FEAT_GRAD_WIDE(104)
+    RPGP_FEAT_GRAD_WIDE(112)
+    RPGP_FEAT_GRAD_WIDE(120)
+    RPGP_FEAT_GRAD_WIDE(128)
     default: return RPGP_EINVAL;
   }
 #undef RPGP_FEAT_GRAD
+#undef RPGP_FEAT_GRAD_WIDE
   return (int)hipGetLastError();
 }
 

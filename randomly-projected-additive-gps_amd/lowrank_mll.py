@@ -2,7 +2,7 @@
 mode of inv_quad_logdet.InvQuadLogDet ("features").
 
 The features of lowrank_posterior.py make the truncated kernel an explicit feature model K_lr = B B^T (B: N x F, F = J r;
-rpgp_lowrank_features_f64).  With r = y - c, M = sigma^2 I + B^T B = L L^T, w = M^-1 B^T r and alpha = (r - B w) / sigma^2
+rpgp_lowrank_features_f64; p <= settings.lowrank_max_rank).  With r = y - c, M = sigma^2 I + B^T B = L L^T, w = M^-1 B^T r and alpha = (r - B w) / sigma^2
 (= Khat^-1 r), everything is F x F algebra in float64:
     inv_quad = r^T alpha,                    logdet = (N - F) log sigma^2 + log|M|,
     tr(Khat^-1) = (N - F) / sigma^2 + tr(M^-1),          tr(Khat^-1 K_lr) = F - sigma^2 tr(M^-1),
@@ -24,7 +24,7 @@ import torch
 
 from . import backend as _backend
 from . import ops, settings
-from .lowrank_posterior import MAX_FEATURES, MAX_J, MEMORY_SHARE, LowrankPosterior, tail_tolerance
+from .lowrank_posterior import MAX_FEATURES, MAX_J, MEMORY_SHARE, LowrankPosterior, rank_cap, tail_tolerance
 
 
 class FeatureForm:
@@ -36,6 +36,7 @@ class FeatureForm:
         self.mid, self.inv_w, self.h, self.p, self.r, self.tail, self.G = \
             form.mid, form.inv_w, form.h, form.p, form.r, form.tail, form.G
         self.B, self.L, self.noise, self.scale, self.weight = B, L, noise, scale, weight
+        self.kw = form.kw
 
     @property
     def ranks(self):
@@ -68,9 +69,10 @@ def decide(op, noise):
     scale = float(op._scale)
     Z = op.Z1.detach().double().contiguous()
     mid, h = LowrankPosterior._interval(Z.min(0).values, Z.max(0).values)
-    p, r, tail, G = be.lowrank_post_select(h, tail_tolerance(N, scale * J, noise))
+    cap = rank_cap()[0]
+    p, r, tail, G = be.lowrank_post_select(h, tail_tolerance(N, scale * J, noise), cap)
     if p == 0:
-        return None, "half-width %.3g needs a Chebyshev rank above 64" % h
+        return None, "half-width %.3g needs a Chebyshev rank above %d" % (h, cap)
     F = J * r
     if F >= N:
         return None, "%d features for %d rows (F >= N)" % (F, N)
@@ -80,7 +82,7 @@ def decide(op, noise):
         return None, "the %d x %d features and B M^-1 exceed %.0f%% of the device memory" % (N, F, 100 * MEMORY_SHARE)
     from .lowrank_posterior import _Form
     form = _Form(mid, h, p, r, tail, G)
-    B = be.lowrank_features(Z, form.mid, form.inv_w, form.G, scale)
+    B = be.lowrank_features(Z, form.mid, form.inv_w, form.G, scale, **form.kw)
     M = B.t() @ B
     M.diagonal().add_(noise)
     L, info = torch.linalg.cholesky_ex(M)
@@ -124,7 +126,7 @@ def backward(ctx, g_inv_quad, g_logdet):
         Y = B @ Minv                                                             # Khat^-1 B = B M^-1
         be = _backend.get_backend()
         gZ = be.lowrank_features_grad(fm.Z, fm.mid, fm.inv_w, fm.G, fm.scale, Y, alpha, v, -2.0 * g_iq,
-                                      2.0 * g_ld).to(dtype)
+                                      2.0 * g_ld, **fm.kw).to(dtype)
     if need[1]:
         # K = scale k with scale = outputscale * weight: dK / doutputscale = weight K / scale
         gs = (fm.weight / fm.scale) * (-g_iq * (v * v).sum() + g_ld * (F - noise * tr_minv))

@@ -5,6 +5,7 @@ Every 1-D term is exp2(-h^2 (x - y)^2) ~= T(x)^T C T(y) on x = (z - mid) kappa /
 (p x p, positive semi-definite) ~= G G^T with G = Q_r Lambda_r^1/2 (rpgp_lowrank_post_select).  The truncated kernel is then
 an explicit feature model
     K_lr = B B^T,   B = sqrt(scale) [T(x_1) G | ... | T(x_J) G]   (N x F,  F = J r;  rpgp_lowrank_features_f64)
+(p <= settings.lowrank_max_rank: 64 by default, up to 128)
 whose posterior needs no N x N object.  With M = sigma^2 I + B^T B = L L^T (F x F) and w = M^-1 B^T (y - c):
     mean* = B* w + c,   Sigma* = sigma^2 B* M^-1 B*^T = sigma^2 V^T V  (V = L^-1 B*^T),   alpha = (r - B w) / sigma^2,
     Khat^-1 X = (X - B M^-1 B^T X) / sigma^2,
@@ -40,12 +41,21 @@ MEMORY_SHARE = 0.25              # B (8 N F bytes) may take this share of the de
 _PANEL = 4096                    # columns per triangular solve
 
 
+def rank_cap():
+    """(cap, kw): settings.lowrank_max_rank and the keyword that carries it to the backend's feature kernels.  At the default
+    the keyword is left out, so a backend written against the rank-64 interface keeps serving it."""
+    from . import settings
+    cap = settings.lowrank_max_rank.value()
+    return cap, ({} if cap == 64 else {"max_rank": cap})
+
+
 class _Form:
     """The features of one interval: mid (J), inv_w, ranks, tail and G, and B with its F x F factor."""
 
     def __init__(self, mid, h, p, r, tail, G):
         self.mid, self.h, self.p, self.r, self.tail, self.G = mid, h, p, r, tail, G
         self.inv_w = KAPPA / h if h > 0.0 else 0.0
+        self.kw = rank_cap()[1]                     # the cap this form was selected under goes with it to the kernels
 
 
 class LowrankPosterior:
@@ -76,9 +86,10 @@ class LowrankPosterior:
         """(form, None) for the interval of [zmin, zmax], or (None, reason)."""
         N, J = Z.shape
         mid, h = LowrankPosterior._interval(zmin, zmax)
-        p, r, tail, G = be.lowrank_post_select(h, tail_tolerance(N, scale * J, noise))
+        cap = rank_cap()[0]
+        p, r, tail, G = be.lowrank_post_select(h, tail_tolerance(N, scale * J, noise), cap)
         if p == 0:
-            return None, "half-width %.3g needs a Chebyshev rank above 64" % h
+            return None, "half-width %.3g needs a Chebyshev rank above %d" % (h, cap)
         F = J * r
         if F > MAX_FEATURES:
             return None, "%d features exceed %d" % (F, MAX_FEATURES)
@@ -89,7 +100,7 @@ class LowrankPosterior:
     @staticmethod
     def _factor(be, Z, form, scale, noise, r64):
         """(B, M, L, w) of one form, or None when M = sigma^2 I + B^T B does not factor."""
-        B = be.lowrank_features(Z, form.mid, form.inv_w, form.G, scale)
+        B = be.lowrank_features(Z, form.mid, form.inv_w, form.G, scale, **form.kw)
         M = B.t() @ B
         M.diagonal().add_(noise)
         L, info = torch.linalg.cholesky_ex(M)
@@ -176,7 +187,7 @@ class LowrankPosterior:
             self.zmin, self.zmax = zmin, zmax
             self._set(form, *fac)
             self.rebuilds += 1
-        return be.lowrank_features(Zs, self.form.mid, self.form.inv_w, self.form.G, self.scale)
+        return be.lowrank_features(Zs, self.form.mid, self.form.inv_w, self.form.G, self.scale, **self.form.kw)
 
     # ---- prediction ----------------------------------------------------------------------------------------------------
     def predict(self, xs, at_train=False):

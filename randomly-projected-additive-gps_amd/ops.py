@@ -342,9 +342,21 @@ def lowrank_post_select(h, tol, p_max=64):
     return p, r, float(tail.value), G[:p, :r].copy()
 
 
-def lowrank_features(Z, mid, inv_w, G, scale, out=None):
+LOWRANK_FEATURE_RANK = 128      # largest p of rpgp_lowrank_features_f64 / rpgp_lowrank_features_grad_f64
+
+
+def _check_feature_rank(what, p, max_rank):
+    """The cap of one call: p <= max_rank <= 128 (the default 64 is the rank served before the wide instantiations)."""
+    if not 1 <= max_rank <= LOWRANK_FEATURE_RANK:
+        raise ValueError("%s: max_rank = %r outside 1 ... %d" % (what, max_rank, LOWRANK_FEATURE_RANK))
+    if p > max_rank:
+        raise ValueError("%s: p = %d exceeds max_rank = %d" % (what, p, max_rank))
+
+
+def lowrank_features(Z, mid, inv_w, G, scale, out=None, max_rank=64):
     """B (N x J r float64) with B[i, j r + k] = sqrt(scale) sum_m T_m((Z[i, j] - mid[j]) inv_w) G[m, k]
-    (rpgp_lowrank_features_f64): the explicit features of the truncated kernel, K_lr = B B^T."""
+    (rpgp_lowrank_features_f64): the explicit features of the truncated kernel, K_lr = B B^T.  ValueError for p > max_rank or
+    max_rank > 128."""
     import math
     lib = _lib.load()
     Z = _require(Z, "Z", 2, allow64=True)
@@ -353,6 +365,7 @@ def lowrank_features(Z, mid, inv_w, G, scale, out=None):
     N, J = Z.shape
     Gt = torch.as_tensor(G, dtype=torch.float64).to(Z.device).contiguous()
     p, r = Gt.shape
+    _check_feature_rank("lowrank_features", p, max_rank)
     mid_t = torch.as_tensor(mid, dtype=torch.float64).to(Z.device).reshape(-1).contiguous()
     if mid_t.numel() != J:
         raise ValueError("mid must have one entry per projection")
@@ -378,10 +391,11 @@ def chebyshev_derivative(G):
     return D[:p].copy()
 
 
-def lowrank_features_grad(Z, mid, inv_w, G, scale, Y, alpha, v, ca, cy, out=None):
+def lowrank_features_grad(Z, mid, inv_w, G, scale, Y, alpha, v, ca, cy, out=None, max_rank=64):
     """gZ (N x J float64) = dL/dZ for dL/dB = W = ca alpha v^T + cy Y through B = lowrank_features(Z, mid, inv_w, G, scale)
     (rpgp_lowrank_features_grad_f64, with the derivative coefficients of G formed here).  `out`: an N x J float64 view with unit
-    column stride and any row stride (its columns beyond J are not touched).  ValueError outside J <= 64, r <= p <= 64."""
+    column stride and any row stride (its columns beyond J are not touched).  ValueError outside J <= 64, r <= p <= max_rank
+    <= 128."""
     import math
     lib = _lib.load()
     Z = _require(Z, "Z", 2, allow64=True)
@@ -392,9 +406,10 @@ def lowrank_features_grad(Z, mid, inv_w, G, scale, Y, alpha, v, ca, cy, out=None
     if Gd.ndim != 2:
         raise ValueError("G must be p x r")
     p, r = Gd.shape
-    if N < 1 or not 1 <= J <= 64 or not 1 <= r <= p <= 64:
-        raise ValueError("lowrank_features_grad: N = %d, J = %d, p = %d, r = %d outside N >= 1, J <= 64, r <= p <= 64"
-                         % (N, J, p, r))
+    _check_feature_rank("lowrank_features_grad", p, max_rank)
+    if N < 1 or not 1 <= J <= 64 or not 1 <= r <= p:
+        raise ValueError("lowrank_features_grad: N = %d, J = %d, p = %d, r = %d outside N >= 1, J <= 64, r <= p <= %d"
+                         % (N, J, p, r, max_rank))
     dev = Z.device
     Gd_t = torch.from_numpy(Gd).to(dev).contiguous()
     mid_t = torch.as_tensor(mid, dtype=torch.float64).to(dev).reshape(-1).contiguous()

@@ -252,6 +252,8 @@ def build_parser():
                    help="(rpgp) predict in closed form from the explicit features of the Chebyshev low-rank kernel where served")
     p.add_argument("--lowrank_mll", action="store_true",
                    help="(rpgp) train on the closed-form marginal likelihood of the Chebyshev low-rank features where served")
+    p.add_argument("--lowrank_max_rank", type=int, default=64, metavar="N",
+                   help="(rpgp) largest Chebyshev rank served by --lowrank_posterior / --lowrank_mll (1 ... 128, default 64)")
     return p
 
 
@@ -405,7 +407,8 @@ def main(argv=None, rank_entry=None):
                 settings.memory_efficient(args.memory_efficient), settings.cache_kernel(args.cache_kernel), \
                 settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)), \
                 settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)), \
-                settings.lowrank_mll(getattr(args, "lowrank_mll", False)):
+                settings.lowrank_mll(getattr(args, "lowrank_mll", False)), \
+                settings.lowrank_max_rank(getattr(args, "lowrank_max_rank", 64)):
             if args.ablation:
                 if args.k is not None:
                     abl_vars = args.k

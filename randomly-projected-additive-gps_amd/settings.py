@@ -138,18 +138,40 @@ native_sharded_cg = _setting("native_sharded_cg", True, flag=True)
 # or neither, decided once per operator.  Off: the exact sweep.  RPGP_LOWRANK=0 and RPGP_FACT_ASM keep the sweep either way.
 lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
 # prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
-# with a float64 twin (k = 1, no grid), J <= 64, at most 4096 features in 25 % of the device memory gets its posterior mean,
-# covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
+# with a float64 twin (k = 1, no grid), J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default, up to 128), at most 4096
+# features in 25 % of the device memory gets its posterior mean, covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
 # where it is not served: the prediction strategy as before.
 lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
 # training on the exact marginal likelihood of the same truncated kernel in closed form (lowrank_mll.py): value and full
 # gradient from the explicit features B (K_lr = B B^T) through F x F factorisations in float64: no probes, no CG, no SLQ, the
 # same deterministic function for the value and the gradient (what an L-BFGS line search needs).  Decided once per operator
 # (AdditiveRPOperator.lowrank_mll_form): an unsharded plain additive-RP RBF operator (k = 1, no grid, not memory-efficient),
-# J <= 64, Chebyshev rank p <= 64 at lowrank_posterior's tail tolerance, F < N, F <= 4096, B and B M^-1 in 25 % of the device
+# J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default) at lowrank_posterior's tail tolerance, F < N, F <= 4096, B and B M^-1 in 25 % of the device
 # memory.  Where served it takes precedence over lowrank_kernel and over the Cholesky regime (use_cholesky); where not, the
 # step runs exactly as with the setting off (lowrank_kernel then applies as before).
 lowrank_mll = _setting("lowrank_mll", False, flag=True)
+
+
+# the largest Chebyshev rank p that lowrank_posterior and lowrank_mll serve: 64 covers a half-width of the 1-D term of about 7.3
+# (tail 1e-10) in the units of exp2(-h^2 (x - y)^2), 128 about 14 (the degree-128 reference resolves no more).  Above 64 the
+# feature kernels stage G in dynamic LDS and the selection uses a tridiagonal eigensolver; at or below 64 nothing changes with
+# this setting, bit for bit.  lowrank_kernel (the float32 product kernels) keeps its own cap of 64.
+class lowrank_max_rank(_Setting):
+    _default = 64
+    _value = None
+
+    def __init__(self, value):
+        super().__init__(_checked_max_rank(value))
+
+    @classmethod
+    def _set(cls, v):
+        cls._value = None if v is None else _checked_max_rank(v)
+
+
+def _checked_max_rank(value):
+    if isinstance(value, bool) or int(value) != value or not 1 <= int(value) <= 128:
+        raise ValueError("lowrank_max_rank must be an integer in 1 ... 128, got %r" % (value,))
+    return int(value)
 
 
 class fast_computations:

@@ -18,6 +18,7 @@ def _recording(self, noise=None):
     r = _orig(self, noise)
     _last["served"] = r is not None
     _last["ranks"] = r.ranks if r is not None else None
+    _last["reason"] = self.lowrank_mll_reason
     return r
 
 
@@ -81,7 +82,7 @@ def steps(name, N, d, J, mode, n_steps, warmup, half_width, out):
                   file=sys.stderr, flush=True)
     st = sorted(times)
     res = {"kind": "step", "config": name, "N": N, "d": d, "J": J, "mode": mode, "half_width": half_width,
-           "steps": n_steps, "warmup": warmup, "step_ms_median": 1e3 * st[len(st) // 2], "step_ms_min": 1e3 * st[0],
+           "max_rank": settings.lowrank_max_rank.value(), "steps": n_steps, "warmup": warmup, "step_ms_median": 1e3 * st[len(st) // 2], "step_ms_min": 1e3 * st[0],
            "step_ms_max": 1e3 * st[-1], "served_steps": sum(served) if mode == "mll" else None,
            "ranks_pr_F": ranks[-1] if mode == "mll" else None}
     _emit(res, out)
@@ -98,10 +99,22 @@ def stages(name, N, d, J, half_width, out):
         s = float(model.covar_module.outputscale) / J
         noise = float(lik.noise)
         mid, h = LowrankPosterior._interval(Z.min(0).values, Z.max(0).values)
-        p, r, tail, G = ops.lowrank_post_select(h, tail_tolerance(N, s * J, noise))
+        cap = settings.lowrank_max_rank.value()
+        tol = tail_tolerance(N, s * J, noise)
+        p, r, tail, G = ops.lowrank_post_select(h, tol, cap)
+        if p == 0:
+            _emit({"kind": "stages", "config": name, "N": N, "J": J, "half_width": half_width, "max_rank": cap, "served": False},
+                  out)
+            return
+        ts = []
+        for _ in range(5):                                # the host selection (no device work)
+            t0 = time.perf_counter()
+            ops.lowrank_post_select(h, tol, cap)
+            ts.append(time.perf_counter() - t0)
+        t_select = 1e3 * sorted(ts)[2]
         f = _Form(mid, h, p, r, tail, G)
         F = J * r
-        t_feat, B = _timed(lambda: ops.lowrank_features(Z, f.mid, f.inv_w, f.G, s))
+        t_feat, B = _timed(lambda: ops.lowrank_features(Z, f.mid, f.inv_w, f.G, s, max_rank=cap))
         t_gram, M = _timed(lambda: B.t() @ B)
         M.diagonal().add_(noise)
         t_chol, L = _timed(lambda: torch.linalg.cholesky_ex(M)[0])
@@ -109,9 +122,10 @@ def stages(name, N, d, J, half_width, out):
         t_y, Y = _timed(lambda: B @ Minv)
         alpha = torch.randn(N, 1, dtype=torch.float64, device=dev)
         v = B.t() @ alpha
-        t_grad, _ = _timed(lambda: ops.lowrank_features_grad(Z, f.mid, f.inv_w, f.G, s, Y, alpha, v, -1.0, 1.0))
+        t_grad, _ = _timed(lambda: ops.lowrank_features_grad(Z, f.mid, f.inv_w, f.G, s, Y, alpha, v, -1.0, 1.0, max_rank=cap))
     read = 8.0 * (N * F + N * J + N + F)                 # Y, Z, alpha, v
     res = {"kind": "stages", "config": name, "N": N, "J": J, "p": p, "r": r, "F": F, "half_width": half_width,
+           "max_rank": cap, "tail": tail, "select_host_ms": t_select,
            "features_ms": t_feat, "gram_ms": t_gram, "cholesky_ms": t_chol, "cholesky_inverse_ms": t_minv, "Y_ms": t_y,
            "grad_kernel_ms": t_grad, "grad_kernel_read_TBps": read / (t_grad * 1e-3) / 1e12,
            "features_write_TBps": 8.0 * N * F / (t_feat * 1e-3) / 1e12, "grad_over_features": t_grad / t_feat}
@@ -124,7 +138,7 @@ def lbfgs_fit(name, N, d, J, half_width, max_iter, out):
     mll = ExactMarginalLogLikelihood(lik, model)
     params = [p for p in model.parameters() if p.requires_grad]
     opt = torch.optim.LBFGS(params, lr=1.0, max_iter=max_iter, line_search_fn="strong_wolfe")
-    evals, served = [0], [0]
+    evals, served, reasons = [0], [0], []
 
     def closure():
         opt.zero_grad()
@@ -133,6 +147,8 @@ def lbfgs_fit(name, N, d, J, half_width, max_iter, out):
         loss.backward()
         evals[0] += 1
         served[0] += bool(_last.get("served", False))
+        if evals[0] > 1 and not _last.get("served", False):
+            reasons.append(_last.get("reason"))
         return loss
 
     with settings.lowrank_mll(True):
@@ -145,8 +161,9 @@ def lbfgs_fit(name, N, d, J, half_width, max_iter, out):
         final = float(mll.negative(model(X), y))
     st = opt.state[opt._params[0]]
     res = {"kind": "lbfgs", "config": name, "N": N, "J": J, "half_width": half_width, "max_iter": max_iter,
+           "max_rank": settings.lowrank_max_rank.value(),
            "lbfgs_iterations": int(st["n_iter"]), "evaluations": evals[0] - 1, "served_evaluations": served[0] - 1,
-           "wall_s": wall, "loss_first": first, "loss_final": final}
+           "unserved_reasons": reasons, "wall_s": wall, "loss_first": first, "loss_final": final}
     _emit(res, out)
 
 
@@ -167,8 +184,10 @@ if __name__ == "__main__":
     ap.add_argument("--half_width", type=float, default=4.6)
     ap.add_argument("--stages", action="store_true", help="also time the stages of one features-mode evaluation")
     ap.add_argument("--lbfgs", type=int, default=0, help="also run one L-BFGS fit of at most this many iterations")
+    ap.add_argument("--max_rank", type=int, default=64, help="settings.lowrank_max_rank for every measurement (1 ... 128)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     a = ap.parse_args()
+    settings.lowrank_max_rank._set(a.max_rank)
     table = {"C4": ("C4 synthetic 50k RPA-GP", 50000, 20, 20),
              "C5X": ("C5-sized exact RPA-GP (synthetic, J=20, no SKI)", 391386, 20, 20)}
     for c in a.configs.split(","):

@@ -72,6 +72,7 @@ def bench(name, N, d, J, n_test, half_width, sides, modes, out_path, reps):
             t_build, _ = timed(lambda: model(Xs[:1]))        # strategy build (+ one row)
             st = model.prediction_strategy
             rec = {"config": name, "N": N, "d": d, "J": J, "n_test": n_test, "half_width": half_width, "setting": on,
+                   "max_rank": settings.lowrank_max_rank.value(),
                    "served": st.lowrank is not None, "strategy_build_s": round(t_build, 4)}
             if on and st.lowrank is not None:
                 lr = st.lowrank
@@ -79,11 +80,11 @@ def bench(name, N, d, J, n_test, half_width, sides, modes, out_path, reps):
                 rec.update({"p": p, "r": r, "F": F, "tail": lr.form.tail, "rebuilds": lr.rebuilds})
                 be = backend.get_backend()
                 f = lr.form
-                t_feat, _ = timed(lambda: be.lowrank_features(lr.Z, f.mid, f.inv_w, f.G, lr.scale), reps=5)
+                t_feat, _ = timed(lambda: be.lowrank_features(lr.Z, f.mid, f.inv_w, f.G, lr.scale, **f.kw), reps=5)
                 t_gram, M = timed(lambda: lr.B.t() @ lr.B, reps=3)
                 t_fac, L = timed(lambda: torch.linalg.cholesky(lr.M), reps=3)
                 Zs = lr._test_coordinates(Xs)
-                t_tfeat, Bs = timed(lambda: be.lowrank_features(Zs, f.mid, f.inv_w, f.G, lr.scale), reps=3)
+                t_tfeat, Bs = timed(lambda: be.lowrank_features(Zs, f.mid, f.inv_w, f.G, lr.scale, **f.kw), reps=3)
                 t_solve, _ = timed(lambda: lr._lower_solve(Bs.t()), reps=3)
                 rec.update({"features_ms": round(1e3 * t_feat, 3),
                             "features_write_TBps": round(8.0 * N * F / t_feat / 1e12, 3),
@@ -111,8 +112,10 @@ def main():
     ap.add_argument("--half_width", type=float, default=4.6)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--off", action="store_true", help="also time the setting-off path")
+    ap.add_argument("--max_rank", type=int, default=64, help="settings.lowrank_max_rank for every measurement (1 ... 128)")
     ap.add_argument("--out", default="profiles/lowrank_posterior_bench_c4.jsonl")
     a = ap.parse_args()
+    settings.lowrank_max_rank._set(a.max_rank)
     if a.config == "c4":
         bench("C4", 50000, 20, 20, 2000, a.half_width, [True, False] if a.off else [True],
               {True: ["full", "var", "mean"], False: ["full", "mean"]}, a.out, a.reps)
