@@ -22,11 +22,19 @@
 //   (b) combine  U^R_j = scale D W^R_j, U^L_j = scale D W^L_j (float64), and gscale_jt = W^L_j[:,t]^T C W^R_j[:,t]
 //   (c) output   gZ_ij = sum_m T_m(x_ij) q_m,  q_m = sum_t L_it U^R_j[m][t] + R_it U^L_j[m][t]  (float64, one Clenshaw sum);
 //                the first workgroup also sums the gscale_jt in a fixed order
+//
+// Explicit features (rpgp_lowrank_post_select, rpgp_lowrank_features_f64, rpgp_lowrank_features_grad_f64): C = G G^T on the
+// host, then B = sqrt(scale) [T(x_1) G | ... | T(x_J) G] and its adjoint in float64 on v_mfma_f64_16x16x4_f64.  Both kernels are
+// one body (lr_features_body) with an epilogue each, for every padded rank 8 ... 128: G in static LDS up to 64, in dynamic LDS
+// above.
+//
+// Every kernel is templated on the padded rank; dispatch_pb turns the runtime value into the template argument.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rpgp.h"
@@ -527,30 +535,6 @@ int launch_grad(const LowrankPlan &P, const float *L, const float *R, float *gZ,
   return (int)hipGetLastError();
 }
 
-// (PB < QB never occurs: PB = pad8(max(p, q)) >= QB)
-template <int PB, int QB>
-int launch_grad_if(const LowrankPlan &P, const float *L, const float *R, float *gZ, float *gscale, int N, int ldg, int T,
-                   int j0, int jn, float scale, void *ws, hipStream_t st) {
-  if constexpr (PB >= QB) return launch_grad<PB, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-  return RPGP_EINVAL;
-}
-
-template <int QB>
-int dispatch_grad_pb(const LowrankPlan &P, const float *L, const float *R, float *gZ, float *gscale, int N, int ldg, int T,
-                     int j0, int jn, float scale, void *ws, hipStream_t st) {
-  switch (grad_pb(P)) {
-    case 8: return launch_grad_if<8, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 16: return launch_grad_if<16, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 24: return launch_grad_if<24, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 32: return launch_grad_if<32, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 40: return launch_grad_if<40, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 48: return launch_grad_if<48, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 56: return launch_grad_if<56, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    case 64: return launch_grad_if<64, QB>(P, L, R, gZ, gscale, N, ldg, T, j0, jn, scale, ws, st);
-    default: return RPGP_EINVAL;
-  }
-}
-
 // ---- explicit features of the posterior (rpgp_lowrank_post_select / rpgp_lowrank_features_f64) --------------------------
 // C (p x p, symmetric PSD up to rounding: a congruence of the kernel's Gram matrix at the Chebyshev points) = Q diag(l) Q^T by
 // cyclic Jacobi rotations in double (a fixed sweep order: deterministic).  a: p x p row-major, overwritten; q: eigenvectors as
@@ -726,152 +710,23 @@ void tridiagonal_ql_eigh(const std::vector<double> &a, int p, std::vector<double
 }
 
 constexpr int kFeatRows = 64;            // rows per workgroup (4 waves x 16 rows, all projections)
-constexpr int kFeatLd = 80;              // LDS row stride of G in doubles: rows 4s + kq of one read land 32 banks apart
+constexpr int kFeatLd = 80;              // LDS row stride of G in doubles (PB <= 64): rows 4s + kq of one read land 32 banks apart
 
 typedef double double4v __attribute__((ext_vector_type(4)));
 
-// B[i ldb + j r + k] = sqrt_scale * sum_{m < p} T_m(x_ij) G[m r + k],  x_ij = (Z[i ldz + j] - mid[j]) inv_w.
-// G (zero-padded to PB x 64) is staged in LDS once per workgroup; a wave takes 16 rows and, for each projection, forms the
-// (16 x PB) Chebyshev tile in registers (lane l: row l & 15, T_m for m = 4s + (l >> 4)) and multiplies it by G's column
-// tiles of 16 on v_mfma_f64_16x16x4_f64 (A[row l&15][k l>>4], B[k l>>4][col l&15]; D col l&15, row (l>>4) + 4 reg).
-// Every store: 4 rows x 16 consecutive doubles.  grid (ceil(N / 64))
-template <int PB>
-__global__ __launch_bounds__(256) void lr_features_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
-                                                          const double *__restrict__ mid, double inv_w,
-                                                          const double *__restrict__ G, int p, int r, double sqrt_scale,
-                                                          double *__restrict__ B, long long ldb) {
-  __shared__ double gs[PB * kFeatLd];
-  for (int e = threadIdx.x; e < PB * 64; e += 256) {
-    const int m = e >> 6, k = e & 63;
-    gs[m * kFeatLd + k] = (m < p && k < r) ? G[m * r + k] : 0.0;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int c16 = lane & 15, kq = lane >> 4;
-  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
-  const long long row = rbase + c16;
-  const bool ok = row < N;
-  const int nct = (r + 15) >> 4;
-  for (int j = 0; j < J; ++j) {
-    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0, x2 = 2.0 * x;
-    double a[PB / 4];
-    double tm2 = 1.0, tm1 = x;
-    a[0] = kq == 0 ? 1.0 : (kq == 1 ? x : 0.0);
-#pragma unroll
-    for (int m = 2; m < PB; ++m) {                        // T_m = 2x T_{m-1} - T_{m-2}; lane keeps m = 4s + kq
-      const double tm = __builtin_fma(x2, tm1, -tm2);
-      if ((m & 3) == kq) a[m >> 2] = tm;
-      tm2 = tm1;
-      tm1 = tm;
-    }
-    for (int ct = 0; ct < nct; ++ct) {
-      double4v acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < PB / 4; ++s)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gs[(4 * s + kq) * kFeatLd + ct * 16 + c16], acc, 0, 0, 0);
-      const int col = ct * 16 + c16;
-      if (col < r) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const long long ro = rbase + kq + 4 * i;
-          if (ro < N) B[ro * ldb + (long long)j * r + col] = sqrt_scale * acc[i];
-        }
-      }
-    }
-  }
-}
-
-// The adjoint of lr_features_kernel (rpgp_lowrank_features_grad_f64): with W = ca alpha v^T + cy Y (N x J r, never stored),
-//   gZ[i ldg + j] = fac * sum_{k < r} (sum_{m < p} T_m(x_ij) Gd[m r + k]) W[i, j r + k],   fac = sqrt_scale inv_w,
-// Gd the derivative coefficients of G (sum_m T'_m G[m, k] = sum_m T_m Gd[m, k]).  The same tiles as lr_features_kernel: Gd in
-// LDS, the (16 x PB) Chebyshev tile of a wave's 16 rows in registers, v_mfma_f64_16x16x4_f64 per column tile of 16.  Each
-// product tile (lane: col l & 15, rows (l >> 4) + 4 i) is multiplied element-wise by W read as 4 rows x 16 consecutive doubles
-// of Y, summed over the column tiles in the lane, then over the 16 lanes of a row by xor-shuffles 8, 4, 2, 1 (a fixed order);
-// lane l & 15 == 0 writes each (i, j) once.  grid (ceil(N / 64))
-template <int PB>
-__global__ __launch_bounds__(256) void lr_features_grad_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
-                                                               const double *__restrict__ mid, double inv_w,
-                                                               const double *__restrict__ Gd, int p, int r, double fac,
-                                                               const double *__restrict__ Y, long long ldy,
-                                                               const double *__restrict__ alpha, const double *__restrict__ v,
-                                                               double ca, double cy, double *__restrict__ gZ, long long ldg) {
-  __shared__ double gs[PB * kFeatLd];
-  for (int e = threadIdx.x; e < PB * 64; e += 256) {
-    const int m = e >> 6, k = e & 63;
-    gs[m * kFeatLd + k] = (m < p && k < r) ? Gd[m * r + k] : 0.0;
-  }
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int c16 = lane & 15, kq = lane >> 4;
-  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
-  const long long row = rbase + c16;
-  const bool ok = row < N;
-  const int nct = (r + 15) >> 4;
-  double al[4];                                           // ca alpha of the lane's output rows kq + 4 i
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const long long ro = rbase + kq + 4 * i;
-    al[i] = ro < N ? ca * alpha[ro] : 0.0;
-  }
-  for (int j = 0; j < J; ++j) {
-    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0, x2 = 2.0 * x;
-    double a[PB / 4];
-    double tm2 = 1.0, tm1 = x;
-    a[0] = kq == 0 ? 1.0 : (kq == 1 ? x : 0.0);
-#pragma unroll
-    for (int m = 2; m < PB; ++m) {                        // T_m = 2x T_{m-1} - T_{m-2}; lane keeps m = 4s + kq
-      const double tm = __builtin_fma(x2, tm1, -tm2);
-      if ((m & 3) == kq) a[m >> 2] = tm;
-      tm2 = tm1;
-      tm1 = tm;
-    }
-    double part[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int ct = 0; ct < nct; ++ct) {
-      double4v acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < PB / 4; ++s)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gs[(4 * s + kq) * kFeatLd + ct * 16 + c16], acc, 0, 0, 0);
-      const int col = ct * 16 + c16;
-      if (col < r) {
-        const long long f = (long long)j * r + col;
-        const double vc = v[f];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const long long ro = rbase + kq + 4 * i;
-          if (ro < N) part[i] = __builtin_fma(acc[i], __builtin_fma(cy, Y[ro * ldy + f], al[i] * vc), part[i]);
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      part[i] += __shfl_xor(part[i], 8);
-      part[i] += __shfl_xor(part[i], 4);
-      part[i] += __shfl_xor(part[i], 2);
-      part[i] += __shfl_xor(part[i], 1);
-    }
-    if (c16 == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const long long ro = rbase + kq + 4 * i;
-        if (ro < N) gZ[ro * ldg + j] = fac * part[i];
-      }
-    }
-  }
-}
-
-// ---- padded ranks 72 ... 128 of the two kernels above (r up to p: up to 8 column tiles) -----------------------------------
-// The same tiles, order and stores; G no longer fits the 64 KB of static LDS, so it is staged in dynamic LDS sized from the
-// column tiles in use: PB rows of wide_ld(nct) doubles.  The stride stays = 16 mod 32 doubles: ds_read_b64 serves a 32-lane
-// half per cycle, lanes 0-15 read 16 consecutive doubles (banks 0-31) of row 4s + kq and lanes 16-31 those of the next row,
-// 2 * stride = 32 mod 64 banks further on: no conflict.  LDS per workgroup: PB * wide_ld * 8 bytes, from 27 KB (PB 72, one
-// tile) to 144 KB (PB 128, eight tiles) of the CU's 160 KB, so 5 ... 1 workgroups per CU (DESIGN.md §7.5 has the table).
-// Registers (hipcc 7.2, -O3, gfx950; unified VGPRs, of which 8 are AGPRs), lr_features_wide_kernel | lr_features_grad_wide_kernel,
-// no scratch and no spill in any of them:
-//   PB  72:  80 | 116      PB  80:  84 | 120      PB  88:  88 | 124      PB  96:  92 | 128
-//   PB 104:  96 | 132      PB 112: 100 | 136      PB 120: 104 | 140      PB 128: 108 | 144
-// (the narrow PB 64 kernels: 80 | 116), so registers allow 3 waves per SIMD at worst and LDS is what bounds the occupancy.
+// ---- padded ranks 72 ... 128 (r up to p: up to 8 column tiles) --------------------------------------------------------------
+// G no longer fits the 64 KB of static LDS, so it is staged in dynamic LDS sized from the column tiles in use: PB rows of
+// wide_ld(nct) doubles.  The stride stays = 16 mod 32 doubles: ds_read_b64 serves a 32-lane half per cycle, lanes 0-15 read 16
+// consecutive doubles (banks 0-31) of row 4s + kq and lanes 16-31 those of the next row, 2 * stride = 32 mod 64 banks further
+// on: no conflict.  LDS per workgroup: PB * wide_ld * 8 bytes, from 27 KB (PB 72, one tile) to 144 KB (PB 128, eight tiles) of
+// the CU's 160 KB, so 5 ... 1 workgroups per CU (DESIGN.md §7.5 has the table).
+// Registers (hipcc 7.2, -O3, gfx950; unified VGPRs, of which 8 are AGPRs), lr_features_kernel | lr_features_grad_kernel, no
+// scratch and no spill in any of them:
+//   PB  64:  76 | 108
+//   PB  72:  80 | 112      PB  80:  84 | 116      PB  88:  88 | 120      PB  96:  92 | 124
+//   PB 104:  96 | 128      PB 112: 100 | 132      PB 120: 104 | 136      PB 128: 108 | 140
+// so registers allow 3 waves per SIMD at worst and above PB 64 LDS is what bounds the occupancy.
 constexpr int kFeatMaxRank = 128;        // largest p (and r) of the feature kernels; the float32 product kernels keep kMaxRank
-
 constexpr int wide_ld(int nct) { return ((nct * 16 + 31) & ~31) + 16; }           // 48, 48, 80, 80, 112, 112, 144, 144
 constexpr size_t wide_lds_bytes(int pb, int nct) { return (size_t)pb * wide_ld(nct) * sizeof(double); }
 
@@ -901,85 +756,113 @@ __device__ __forceinline__ void chebyshev_tile(double x, int kq, double (&a)[PB 
   }
 }
 
-// lr_features_kernel for PB in 72 ... 128.  grid (ceil(N / 64)), dynamic LDS wide_lds_bytes(PB, ceil(r / 16))
-template <int PB>
-__global__ __launch_bounds__(256) void lr_features_wide_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
-                                                               const double *__restrict__ mid, double inv_w,
-                                                               const double *__restrict__ G, int p, int r,
-                                                               double sqrt_scale, double *__restrict__ B, long long ldb) {
-  extern __shared__ double gw[];
-  const int nct = (r + 15) >> 4, ld = wide_ld(nct);
-  stage_wide<PB>(gw, G, p, r, nct, ld);
+// what a lane of the feature body knows about its place: its wave's first row, the rows N, the features per projection r, and
+// lane l's column l & 15 and quarter l >> 4 (the product tile's rows kq + 4 i, i < 4)
+struct FeatLane {
+  long long rbase, N;
+  int r, c16, kq;
+};
+
+// The body of both feature kernels.  G (zero-padded to PB rows) is staged in LDS once per workgroup; a wave takes 16 rows and,
+// for each projection, forms the (16 x PB) Chebyshev tile in registers (lane l: row l & 15, T_m for m = 4s + (l >> 4)) and
+// multiplies it by G's column tiles of 16 on v_mfma_f64_16x16x4_f64 (A[row l&15][k l>>4], B[k l>>4][col l&15]; D col l&15,
+// row (l>>4) + 4 reg).  Each product tile whose column is below r goes to the epilogue: init once, then per projection begin,
+// tile per column tile, end.  PB <= 64: G in static LDS, PB x kFeatLd doubles, all 64 columns staged; above: stage_wide.
+template <int PB, typename Epilogue>
+__device__ __forceinline__ void lr_features_body(const double *__restrict__ Z, long long N, int J, int ldz,
+                                                 const double *__restrict__ mid, double inv_w, const double *__restrict__ G,
+                                                 int p, int r, Epilogue ep) {
+  const int nct = (r + 15) >> 4;
+  double *gs;
+  int ld;
+  if constexpr (PB <= 64) {
+    __shared__ double gn[PB * kFeatLd];
+    gs = gn;
+    ld = kFeatLd;
+    for (int e = threadIdx.x; e < PB * 64; e += 256) {
+      const int m = e >> 6, k = e & 63;
+      gs[m * kFeatLd + k] = (m < p && k < r) ? G[m * r + k] : 0.0;
+    }
+    __syncthreads();
+  } else {
+    extern __shared__ double gw[];
+    gs = gw;
+    ld = wide_ld(nct);
+    stage_wide<PB>(gs, G, p, r, nct, ld);
+  }
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int c16 = lane & 15, kq = lane >> 4;
-  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
-  const long long row = rbase + c16;
+  const FeatLane L = {(long long)blockIdx.x * kFeatRows + wv * 16, N, r, lane & 15, lane >> 4};
+  const long long row = L.rbase + L.c16;
   const bool ok = row < N;
-  const double *gl = gw + kq * ld + c16;
+  const double *gl = gs + L.kq * ld + L.c16;
+  ep.init(L);
   for (int j = 0; j < J; ++j) {
     const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0;
     double a[PB / 4];
-    chebyshev_tile<PB>(x, kq, a);
+    chebyshev_tile<PB>(x, L.kq, a);
+    ep.begin();
     for (int ct = 0; ct < nct; ++ct) {
       double4v acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
       for (int s = 0; s < PB / 4; ++s)
         acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gl[4 * s * ld + ct * 16], acc, 0, 0, 0);
-      const int col = ct * 16 + c16;
-      if (col < r) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const long long ro = rbase + kq + 4 * i;
-          if (ro < N) B[ro * ldb + (long long)j * r + col] = sqrt_scale * acc[i];
-        }
-      }
+      const int col = ct * 16 + L.c16;
+      if (col < r) ep.tile(L, j, col, acc);
     }
+    ep.end(L, j);
   }
 }
 
-// lr_features_grad_kernel for PB in 72 ... 128.  grid (ceil(N / 64)), dynamic LDS wide_lds_bytes(PB, ceil(r / 16))
-template <int PB>
-__global__ __launch_bounds__(256) void lr_features_grad_wide_kernel(
-    const double *__restrict__ Z, long long N, int J, int ldz, const double *__restrict__ mid, double inv_w,
-    const double *__restrict__ Gd, int p, int r, double fac, const double *__restrict__ Y, long long ldy,
-    const double *__restrict__ alpha, const double *__restrict__ v, double ca, double cy, double *__restrict__ gZ,
-    long long ldg) {
-  extern __shared__ double gw[];
-  const int nct = (r + 15) >> 4, ld = wide_ld(nct);
-  stage_wide<PB>(gw, Gd, p, r, nct, ld);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int c16 = lane & 15, kq = lane >> 4;
-  const long long rbase = (long long)blockIdx.x * kFeatRows + wv * 16;
-  const long long row = rbase + c16;
-  const bool ok = row < N;
-  const double *gl = gw + kq * ld + c16;
-  double al[4];                                           // ca alpha of the lane's output rows kq + 4 i
+// B[i ldb + j r + k] = sqrt_scale * (product tile).  Every store: 4 rows x 16 consecutive doubles.
+struct FeatStore {
+  double sqrt_scale;
+  double *__restrict__ B;
+  long long ldb;
+  __device__ __forceinline__ void init(const FeatLane &) {}
+  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void tile(const FeatLane &L, int j, int col, const double4v &acc) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const long long ro = rbase + kq + 4 * i;
-    al[i] = ro < N ? ca * alpha[ro] : 0.0;
-  }
-  for (int j = 0; j < J; ++j) {
-    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0;
-    double a[PB / 4];
-    chebyshev_tile<PB>(x, kq, a);
-    double part[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int ct = 0; ct < nct; ++ct) {
-      double4v acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int s = 0; s < PB / 4; ++s)
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[s], gl[4 * s * ld + ct * 16], acc, 0, 0, 0);
-      const int col = ct * 16 + c16;
-      if (col < r) {
-        const long long f = (long long)j * r + col;
-        const double vc = v[f];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const long long ro = rbase + kq + 4 * i;
-          if (ro < N) part[i] = __builtin_fma(acc[i], __builtin_fma(cy, Y[ro * ldy + f], al[i] * vc), part[i]);
-        }
-      }
+    for (int i = 0; i < 4; ++i) {
+      const long long ro = L.rbase + L.kq + 4 * i;
+      if (ro < L.N) B[ro * ldb + (long long)j * L.r + col] = sqrt_scale * acc[i];
     }
+  }
+  __device__ __forceinline__ void end(const FeatLane &, int) {}
+};
+
+// The adjoint: each product tile is multiplied element-wise by W = ca alpha v^T + cy Y read as 4 rows x 16 consecutive doubles
+// of Y, summed over the column tiles in the lane, then over the 16 lanes of a row by xor-shuffles 8, 4, 2, 1 (a fixed order);
+// lane l & 15 == 0 writes each (i, j) once.
+struct FeatAdjoint {
+  double fac;
+  const double *__restrict__ Y;
+  long long ldy;
+  const double *__restrict__ alpha, *__restrict__ v;
+  double ca, cy;
+  double *__restrict__ gZ;
+  long long ldg;
+  double al[4], part[4];                                  // ca alpha of the lane's output rows kq + 4 i; their sums
+  __device__ __forceinline__ void init(const FeatLane &L) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const long long ro = L.rbase + L.kq + 4 * i;
+      al[i] = ro < L.N ? ca * alpha[ro] : 0.0;
+    }
+  }
+  __device__ __forceinline__ void begin() {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) part[i] = 0.0;
+  }
+  __device__ __forceinline__ void tile(const FeatLane &L, int j, int col, const double4v &acc) {
+    const long long f = (long long)j * L.r + col;
+    const double vc = v[f];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const long long ro = L.rbase + L.kq + 4 * i;
+      if (ro < L.N) part[i] = __builtin_fma(acc[i], __builtin_fma(cy, Y[ro * ldy + f], al[i] * vc), part[i]);
+    }
+  }
+  __device__ __forceinline__ void end(const FeatLane &L, int j) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       part[i] += __shfl_xor(part[i], 8);
@@ -987,21 +870,44 @@ __global__ __launch_bounds__(256) void lr_features_grad_wide_kernel(
       part[i] += __shfl_xor(part[i], 2);
       part[i] += __shfl_xor(part[i], 1);
     }
-    if (c16 == 0) {
+    if (L.c16 == 0) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const long long ro = rbase + kq + 4 * i;
-        if (ro < N) gZ[ro * ldg + j] = fac * part[i];
+        const long long ro = L.rbase + L.kq + 4 * i;
+        if (ro < L.N) gZ[ro * ldg + j] = fac * part[i];
       }
     }
   }
+};
+
+// B[i ldb + j r + k] = sqrt_scale * sum_{m < p} T_m(x_ij) G[m r + k],  x_ij = (Z[i ldz + j] - mid[j]) inv_w.
+// grid (ceil(N / 64)); PB > 64: dynamic LDS wide_lds_bytes(PB, ceil(r / 16))
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
+                                                          const double *__restrict__ mid, double inv_w,
+                                                          const double *__restrict__ G, int p, int r, double sqrt_scale,
+                                                          double *__restrict__ B, long long ldb) {
+  lr_features_body<PB>(Z, N, J, ldz, mid, inv_w, G, p, r, FeatStore{sqrt_scale, B, ldb});
 }
 
-// launch of a wide instantiation: above 64 KB the dynamic LDS needs the function attribute (set per call: it belongs to the
-// current device's copy of the kernel)
+// The adjoint of lr_features_kernel (rpgp_lowrank_features_grad_f64): with W = ca alpha v^T + cy Y (N x J r, never stored),
+//   gZ[i ldg + j] = fac * sum_{k < r} (sum_{m < p} T_m(x_ij) Gd[m r + k]) W[i, j r + k],   fac = sqrt_scale inv_w,
+// Gd the derivative coefficients of G (sum_m T'_m G[m, k] = sum_m T_m Gd[m, k]).  Same grid and LDS.
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_grad_kernel(const double *__restrict__ Z, long long N, int J, int ldz,
+                                                               const double *__restrict__ mid, double inv_w,
+                                                               const double *__restrict__ Gd, int p, int r, double fac,
+                                                               const double *__restrict__ Y, long long ldy,
+                                                               const double *__restrict__ alpha, const double *__restrict__ v,
+                                                               double ca, double cy, double *__restrict__ gZ, long long ldg) {
+  lr_features_body<PB>(Z, N, J, ldz, mid, inv_w, Gd, p, r, FeatAdjoint{fac, Y, ldy, alpha, v, ca, cy, gZ, ldg});
+}
+
+// launch of either feature kernel: no dynamic LDS up to PB 64; above 64 KB it needs the function attribute (set per call: it
+// belongs to the current device's copy of the kernel)
 template <typename K, typename... A>
-int launch_wide(K kernel, int pb, int r, dim3 grid, hipStream_t st, A... args) {
-  const size_t bytes = wide_lds_bytes(pb, (r + 15) >> 4);
+int launch_features(K kernel, int pb, int r, dim3 grid, hipStream_t st, A... args) {
+  const size_t bytes = pb > 64 ? wide_lds_bytes(pb, (r + 15) >> 4) : 0;
   if (bytes > 65536) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)wide_lds_bytes(pb, kFeatMaxRank / 16));
@@ -1010,6 +916,35 @@ int launch_wide(K kernel, int pb, int r, dim3 grid, hipStream_t st, A... args) {
   hipLaunchKernelGGL(kernel, grid, dim3(256), bytes, st, args...);
   return (int)hipGetLastError();
 }
+
+// f(std::integral_constant<int, PB>) for the padded rank pb, a multiple of 8 in [8, MAX]; RPGP_EINVAL for any other pb
+template <int MAX, int PB = 8, typename F>
+int dispatch_pb(int pb, F &&f) {
+  if constexpr (PB > MAX)
+    return RPGP_EINVAL;
+  else
+    return pb == PB ? f(std::integral_constant<int, PB>{}) : dispatch_pb<MAX, PB + 8>(pb, f);
+}
+
+// dst[m ld + n] = c_mn for m, n < p, c the kRefDegree-strided coefficients of cheb2d_coefficients
+template <typename T>
+void copy_leading_block(const std::vector<double> &c, int p, T *dst, size_t ld) {
+  for (int m = 0; m < p; ++m)
+    for (int n = 0; n < p; ++n) dst[m * ld + n] = (T)c[(size_t)m * kRefDegree + n];
+}
+
+// rpgp_lowrank_select / rpgp_lowrank_grad_select (deriv): rank, tail and the leading block (leading dimension p_max)
+int select_to_host(double h, int p_max, double tol, bool deriv, int *p_host, double *tail_host, double *coef_host) {
+  if (!p_host || p_max < 1 || p_max > kRefDegree || !(tol > 0.0)) return RPGP_EINVAL;
+  std::vector<double> c;
+  double tail = 0.0;
+  const int p = select_rank(h, p_max, tol < kTailTol ? tol : kTailTol, &tail, c, deriv);
+  *p_host = p;
+  if (tail_host) *tail_host = p ? tail : 0.0;
+  if (coef_host) copy_leading_block(c, p, coef_host, p_max);
+  return 0;
+}
+
 
 // the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
 int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes, int *p_host,
@@ -1027,8 +962,7 @@ int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, v
   if (p == 0) return 0;                                   // not served: the sweep runs
   const int pb = pad8(p);
   std::vector<float> cf((size_t)pb * pb, 0.f);
-  for (int m = 0; m < p; ++m)
-    for (int n = 0; n < p; ++n) cf[(size_t)m * pb + n] = (float)c[(size_t)m * kRefDegree + n];
+  copy_leading_block(c, p, cf.data(), pb);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float *coef = reinterpret_cast<float *>(plan);
   float *xt = coef + (size_t)kMaxRank * kMaxRank;
@@ -1057,16 +991,7 @@ int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, v
 extern "C" {
 
 int rpgp_lowrank_select(double h, int p_max, int *p_host, double *tail_host, double *coef_host) {
-  if (!p_host || p_max < 1 || p_max > kRefDegree) return RPGP_EINVAL;
-  std::vector<double> c;
-  double tail = 0.0;
-  const int p = select_rank(h, p_max, kTailTol, &tail, c);
-  *p_host = p;
-  if (tail_host) *tail_host = p ? tail : 0.0;
-  if (coef_host && p)
-    for (int m = 0; m < p; ++m)
-      for (int n = 0; n < p; ++n) coef_host[(size_t)m * p_max + n] = c[(size_t)m * kRefDegree + n];
-  return 0;
+  return select_to_host(h, p_max, kTailTol, false, p_host, tail_host, coef_host);
 }
 
 size_t rpgp_lowrank_plan_bytes(int64_t N, int J) {
@@ -1113,18 +1038,9 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
   double *part = reinterpret_cast<double *>(workspace);
   float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
   const bool prof = rpgp_internal::prof_open(st);
-  int rc;
-  switch (P->pb) {
-    case 8: rc = launch_lowrank<8>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 16: rc = launch_lowrank<16>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 24: rc = launch_lowrank<24>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 32: rc = launch_lowrank<32>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 40: rc = launch_lowrank<40>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 48: rc = launch_lowrank<48>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 56: rc = launch_lowrank<56>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    case 64: rc = launch_lowrank<64>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st); break;
-    default: return RPGP_EINVAL;
-  }
+  int rc = dispatch_pb<kMaxRank>(P->pb, [&](auto pb) {
+    return launch_lowrank<decltype(pb)::value>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st);
+  });
   if (prof) {
     const int pc = rpgp_internal::prof_close(st);
     if (!rc) rc = pc;
@@ -1133,16 +1049,7 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
 }
 
 int rpgp_lowrank_grad_select(double h, int q_max, double tol, int *q_host, double *tail_host, double *coef_host) {
-  if (!q_host || q_max < 1 || q_max > kRefDegree || !(tol > 0.0)) return RPGP_EINVAL;
-  std::vector<double> c;
-  double tail = 0.0;
-  const int q = select_rank(h, q_max, tol < kTailTol ? tol : kTailTol, &tail, c, true);
-  *q_host = q;
-  if (tail_host) *tail_host = q ? tail : 0.0;
-  if (coef_host && q)
-    for (int m = 0; m < q; ++m)
-      for (int n = 0; n < q; ++n) coef_host[(size_t)m * q_max + n] = c[(size_t)m * kRefDegree + n];
-  return 0;
+  return select_to_host(h, q_max, tol, true, q_host, tail_host, coef_host);
 }
 
 int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoef_bytes, int *q_host, void *stream) {
@@ -1160,11 +1067,9 @@ int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoe
   const int qb = pad8(q);
   // [D: qb x qb][C: pb x pb at 32 KiB], both float64; C is the plan's own selection again (same h, tolerance: same p)
   std::vector<double> d((size_t)qb * qb, 0.0), cc((size_t)P->pb * P->pb, 0.0), cf;
-  for (int m = 0; m < q; ++m)
-    for (int n = 0; n < q; ++n) d[(size_t)m * qb + n] = c[(size_t)m * kRefDegree + n];
+  copy_leading_block(c, q, d.data(), qb);
   if (select_rank(P->h, kMaxRank, P->tol, nullptr, cf) != P->p) return RPGP_EINVAL;
-  for (int m = 0; m < P->p; ++m)
-    for (int n = 0; n < P->p; ++n) cc[(size_t)m * P->pb + n] = cf[(size_t)m * kRefDegree + n];
+  copy_leading_block(cf, P->p, cc.data(), P->pb);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   double *dd = reinterpret_cast<double *>(dcoef), *dc = dd + kMaxRank * kMaxRank;
   hipError_t e = hipMemcpyAsync(dd, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, st);
@@ -1197,19 +1102,16 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
   if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int n = (int)N, jn = j1 - j0;
-  int rc;
-  switch (P->qb) {
-    case 8: rc = dispatch_grad_pb<8>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 16: rc = dispatch_grad_pb<16>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 24: rc = dispatch_grad_pb<24>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 32: rc = dispatch_grad_pb<32>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 40: rc = dispatch_grad_pb<40>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 48: rc = dispatch_grad_pb<48>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 56: rc = dispatch_grad_pb<56>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    case 64: rc = dispatch_grad_pb<64>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st); break;
-    default: return RPGP_EINVAL;
-  }
-  return rc;
+  // (PB < QB never occurs: PB = pad8(max(p, q)) >= QB, so no such kernel is instantiated)
+  return dispatch_pb<kMaxRank>(P->qb, [&](auto qb) {
+    return dispatch_pb<kMaxRank>(grad_pb(*P), [&](auto pb) -> int {
+      constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;
+      if constexpr (PB >= QB)
+        return launch_grad<PB, QB>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st);
+      else
+        return RPGP_EINVAL;
+    });
+  });
 }
 
 int rpgp_lowrank_post_select(double h, double tol, int p_max, int *p_host, int *r_host, double *tail_host, double *G_host) {
@@ -1271,37 +1173,10 @@ int rpgp_lowrank_features_f64(const double *Z, int64_t N, int J, int ldz, const 
     return RPGP_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
-#define RPGP_FEAT(PB)                                                                                                   \
-  case PB:                                                                                                              \
-    hipLaunchKernelGGL(lr_features_kernel<PB>, grid, dim3(256), 0, st, Z, (long long)N, J, ldz, mid, inv_w, G, p, r,       \
-                       sqrt_scale, B, (long long)ldb);                                                                  \
-    break;
-#define RPGP_FEAT_WIDE(PB)                                                                                              \
-  case PB:                                                                                                              \
-    return launch_wide(lr_features_wide_kernel<PB>, PB, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w, G, p, r,         \
-                       sqrt_scale, B, (long long)ldb);
-  switch (pad8(p)) {
-    RPGP_FEAT(8)
-    RPGP_FEAT(16)
-    RPGP_FEAT(24)
-    RPGP_FEAT(32)
-    RPGP_FEAT(40)
-    RPGP_FEAT(48)
-    RPGP_FEAT(56)
-    RPGP_FEAT(64)
-    RPGP_FEAT_WIDE(72)
-    RPGP_FEAT_WIDE(80)
-    RPGP_FEAT_WIDE(88)
-    RPGP_FEAT_WIDE(96)
-    RPGP_FEAT_WIDE(104)
-    RPGP_FEAT_WIDE(112)
-    RPGP_FEAT_WIDE(120)
-    RPGP_FEAT_WIDE(128)
-    default: return RPGP_EINVAL;
-  }
-#undef RPGP_FEAT
-#undef RPGP_FEAT_WIDE
-  return (int)hipGetLastError();
+  return dispatch_pb<kFeatMaxRank>(pad8(p), [&](auto pb) {
+    return launch_features(lr_features_kernel<decltype(pb)::value>, pb, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w, G, p,
+                           r, sqrt_scale, B, (long long)ldb);
+  });
 }
 
 int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, const double *mid, double inv_w,
@@ -1314,37 +1189,10 @@ int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, c
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
   const double fac = sqrt_scale * inv_w;
-#define RPGP_FEAT_GRAD(PB)                                                                                              \
-  case PB:                                                                                                              \
-    hipLaunchKernelGGL(lr_features_grad_kernel<PB>, grid, dim3(256), 0, st, Z, (long long)N, J, ldz, mid, inv_w, Gd, p,   \
-                       r, fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);                                \
-    break;
-#define RPGP_FEAT_GRAD_WIDE(PB)                                                                                         \
-  case PB:                                                                                                              \
-    return launch_wide(lr_features_grad_wide_kernel<PB>, PB, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w, Gd, p, r,   \
-                       fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);
-  switch (pad8(p)) {
-    RPGP_FEAT_GRAD(8)
-    RPGP_FEAT_GRAD(16)
-    RPGP_FEAT_GRAD(24)
-    RPGP_FEAT_GRAD(32)
-    RPGP_FEAT_GRAD(40)
-    RPGP_FEAT_GRAD(48)
-    RPGP_FEAT_GRAD(56)
-    RPGP_FEAT_GRAD(64)
-    RPGP_FEAT_GRAD_WIDE(72)
-    RPGP_FEAT_GRAD_WIDE(80)
-    RPGP_FEAT_GRAD_WIDE(88)
-    RPGP_FEAT_GRAD_WIDE(96)
-    RPGP_FEAT_GRAD_WIDE(104)
-    RPGP_FEAT_GRAD_WIDE(112)
-    RPGP_FEAT_GRAD_WIDE(120)
-    RPGP_FEAT_GRAD_WIDE(128)
-    default: return RPGP_EINVAL;
-  }
-#undef RPGP_FEAT_GRAD
-#undef RPGP_FEAT_GRAD_WIDE
-  return (int)hipGetLastError();
+  return dispatch_pb<kFeatMaxRank>(pad8(p), [&](auto pb) {
+    return launch_features(lr_features_grad_kernel<decltype(pb)::value>, pb, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w,
+                           Gd, p, r, fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);
+  });
 }
 
 }  // extern "C"

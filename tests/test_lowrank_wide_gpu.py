@@ -130,6 +130,28 @@ def test_narrow_ranks_do_not_depend_on_the_cap(gpu_device, h):
                        ops.lowrank_features_grad(Z, mid, inv_w, G, 0.37, Y, alpha, v, -0.7, 1.3))
 
 
+@pytest.mark.parametrize("r", [1, 17])
+def test_narrow_and_wide_staging_give_the_same_bits(gpu_device, r):
+    """G with p = 61 (PB 64: static LDS, stride 80) and the same G with nine zero rows appended (p = 70, PB 72: dynamic LDS) give
+    the same bits in the features and in the adjoint: the two further MFMA steps add exact zeros to the same accumulation chain,
+    and the Chebyshev derivative of zero rows is zero rows.  N = 65: a second wave and a partial row block; r = 17: a partial
+    second column tile; J = 7: more than one projection."""
+    from rpgp_amd import ops
+    G = _random_G(61, r, 3000 + r)
+    Gz = np.concatenate([G, np.zeros((9, r))])
+    for N in (1, 65):
+        for J in (1, 7):
+            g, Z, mid, inv_w = _problem(N, J, N * 100 + J, gpu_device)
+            F = J * r
+            Y = torch.randn(N, F, generator=g, dtype=torch.float64).to(gpu_device)
+            alpha = torch.randn(N, 1, generator=g, dtype=torch.float64).to(gpu_device)
+            v = torch.randn(F, 1, generator=g, dtype=torch.float64).to(gpu_device)
+            assert torch.equal(ops.lowrank_features(Z, mid, inv_w, G, 0.37, max_rank=128),
+                               ops.lowrank_features(Z, mid, inv_w, Gz, 0.37, max_rank=128)), (N, J)
+            assert torch.equal(ops.lowrank_features_grad(Z, mid, inv_w, G, 0.37, Y, alpha, v, -0.7, 1.3, max_rank=128),
+                               ops.lowrank_features_grad(Z, mid, inv_w, Gz, 0.37, Y, alpha, v, -0.7, 1.3, max_rank=128)), (N, J)
+
+
 def test_wide_limits(gpu_device):
     from rpgp_amd import ops
     f64 = dict(dtype=torch.float64, device=gpu_device)
