@@ -12,6 +12,10 @@
 //   (a) project  W_j[n][t]  = sum_i T_n(x_ij) v_it           per (row block, projection, t): block partials
 //   (b) combine  U_j[m][t]  = scale * sum_n c_mn W_j[n][t]   per (projection, t): partials summed in a fixed order
 //   (c) output   out_it     = sum_j sum_m T_m(x_ij) U_j[m][t] (Clenshaw) + noise * v_it
+// The product moves ~4 MB and does ~40 M FMAs at the headline shape, so each kernel is a latency chain rather than a stream,
+// and each requests every global load it needs before its first wait: (a) its 8 rows' x and v, then the recurrence and the sums
+// in float64; (b) a batch of block partials and the thread's chunk of a coefficient row; (c) the lane's coordinates, its element
+// of V and the thread's share of U, which goes through LDS.  DESIGN.md 7.4 and 7.4a have the measurements.
 //
 // Bilinear derivative (rpgp_bilinear_grad's contract, S = L R^T + R L^T).  With g(x, y) = d f / dx, the factor of that
 // contract is  -(z_i - z_i') e(i, i') = (kappa / h) g(x_i, x_i')  (kappa = (2 ln 2)^-1/2: a = (z - mid) kappa), and
@@ -43,6 +47,7 @@
 namespace {
 
 typedef float float2v __attribute__((ext_vector_type(2)));
+typedef float float4v __attribute__((ext_vector_type(4)));
 
 // rpgp_prepare's buffer (rpgp_kernels.hip): [header 64 floats][mid 64 floats][rowdat N*J float2 {a, exp2(-a^2)}][...]
 constexpr int kPrepRowdatOffsetFloats = 128;
@@ -54,6 +59,7 @@ constexpr double kTailTol = 1.0 / (1 << 26);
 constexpr double kKappa = 0.84932180028801907;   // (2 ln 2)^-1/2
 constexpr int kProjRowsPerThread = 8;    // pass (a): 2 048 rows per workgroup
 constexpr int kProjRows = 256 * kProjRowsPerThread;
+constexpr int kCombineBatch = 8;         // pass (b): block partials a thread requests before it adds the first
 constexpr int kOutRows = 64;             // pass (c): 64 rows x 4 projection groups per workgroup
 
 struct LowrankPlan {
@@ -204,10 +210,12 @@ template <int HALF> __device__ __forceinline__ double swap_add(double a, double 
 // (a) block partials part[b][jj][t][0..PB) = sum over the block's rows of T_m(x_ij) v_it.  grid (row blocks, jn, T)
 // The sums are float64 (T_m v exact, then added): W is a sum of N terms of both signs that C turns into a much smaller
 // product — in float32 its rounding alone is ~1e-6 of the result (measured in an emulation at N = 20 011), in float64 ~3e-8.
+// The recurrence runs in float64 too: x and v are widened once per row, then each m is two v_fma_f64 (T_m, then the sum) and no
+// conversion; a float32 recurrence cost a v_fma_f32 and a v_cvt_f64_f32 per m beside the float64 accumulate.
 // The 64 lanes' PB accumulators are summed transposed: two exchange levels (lane ^ 32, lane ^ 16) halve the live values each,
 // leaving PB / 4 per lane (row r of 16 lanes holds m = r PB / 4 + i), which four DPP steps sum inside the row: ~5 PB
 // instructions per wave where PB butterflies took ~23 PB.  The order of the additions is a function of PB alone.
-// PB = 40: 106 VGPR, PB = 48: 121, PB = 64: 154; no scratch.
+// PB = 40: 108 VGPR, PB = 48: 123, PB = 64: 155 (two more than with the float32 recurrence, the same waves per SIMD); no scratch.
 template <int PB>
 __global__ __launch_bounds__(256) void lr_project_kernel(const float *__restrict__ xt, const float *__restrict__ V,
                                                          double *__restrict__ part, int N, int T, int j0, int jn) {
@@ -228,14 +236,14 @@ __global__ __launch_bounds__(256) void lr_project_kernel(const float *__restrict
   for (int m = 0; m < PB; ++m) acc[m] = 0.0;
 #pragma unroll
   for (int u = 0; u < kProjRowsPerThread; ++u) {
-    const float xi = xv[u], v = r0 + u * 256 < N ? vv[u] : 0.f, x2 = 2.f * xi;
-    float tm2 = 1.f, tm1 = xi;
-    acc[0] += (double)v;
-    acc[1] = __builtin_fma((double)xi, (double)v, acc[1]);
+    const double xi = (double)xv[u], v = r0 + u * 256 < N ? (double)vv[u] : 0.0, x2 = 2.0 * xi;
+    double tm2 = 1.0, tm1 = xi;
+    acc[0] += v;
+    acc[1] = __builtin_fma(xi, v, acc[1]);
 #pragma unroll
     for (int m = 2; m < PB; ++m) {
-      const float tm = __builtin_fmaf(x2, tm1, -tm2);     // T_m = 2x T_{m-1} - T_{m-2}
-      acc[m] = __builtin_fma((double)tm, (double)v, acc[m]);
+      const double tm = __builtin_fma(x2, tm1, -tm2);     // T_m = 2x T_{m-1} - T_{m-2}
+      acc[m] = __builtin_fma(tm, v, acc[m]);
       tm2 = tm1;
       tm1 = tm;
     }
@@ -260,60 +268,130 @@ __global__ __launch_bounds__(256) void lr_project_kernel(const float *__restrict
   }
 }
 
-// (b) U[jj][t][m] = scale * sum_n c_mn W[n],  W[n] = sum_b part[b][jj][t][n] (b in a fixed order; float64, U rounded to
-// float32 at the end).  grid (jn, T)
+// (b) U[jj][t][m] = scale * sum_n c_mn W[n],  W[n] = sum_b part[b][jj][t][n] (float64, U rounded to float32 at the end).
+// grid (jn, T).  Thread (g, n) of the G = 256 / PB groups adds the blocks b = g, g + G, ... in that order and the groups' sums
+// are added in the order g = 0 ... G - 1.  The product with C is split the same way: thread (g, m) takes the CH columns
+// n = g CH ... of row m in ascending order (CH = PB / G rounded up to a multiple of 4), and the NCH chunk sums are added in the
+// order g = 0 ... NCH - 1.  The order of every addition is fixed by (nblk, PB) alone.
+// One round trip: a thread requests a batch of kCombineBatch partials (a block past nblk re-reads block nblk - 1 and counts
+// as 0) and its CH coefficients (CH / 4 dwordx4 loads, a chunk past the row's end re-reads the row's last four and is not
+// used) before the first add; nblk <= kCombineBatch G needs no further load, a longer sum loops over batches.  A whole
+// coefficient row per thread would be one chunk less in LDS, but its PB registers cost occupancy from PB = 24 on.
 template <int PB>
 __global__ __launch_bounds__(256) void lr_combine_kernel(const double *__restrict__ part, const float *__restrict__ coef,
                                                          float *__restrict__ U, int nblk, int T, int jn, float scale) {
   constexpr int G = 256 / PB;
+  constexpr int CH = ((PB + G - 1) / G + 3) & ~3, NCH = (PB + CH - 1) / CH;
+  static_assert(NCH <= G, "a chunk of the coefficient row per group");
   __shared__ double sw[G][PB];
   __shared__ double w[PB];
   const int jj = blockIdx.x, t = blockIdx.y;
   const int n = threadIdx.x % PB, g = threadIdx.x / PB;
-  if (g < G) {
-    double s = 0.0;
-    for (int b = g; b < nblk; b += G) s += part[(((size_t)b * jn + jj) * T + t) * PB + n];
-    sw[g][n] = s;
+  const size_t bstride = (size_t)jn * T * PB;
+  const double *p = part + ((size_t)jj * T + t) * PB + n;
+  double pv[kCombineBatch];
+#pragma unroll
+  for (int k = 0; k < kCombineBatch; ++k) {
+    const int b = g + k * G;
+    pv[k] = p[(size_t)(b < nblk ? b : nblk - 1) * bstride];
   }
+  float4v c[CH / 4];
+#pragma unroll
+  for (int k = 0; k < CH / 4; ++k) {
+    const int col = g * CH + 4 * k;
+    c[k] = *reinterpret_cast<const float4v *>(coef + n * PB + (col < PB ? col : PB - 4));
+  }
+  __builtin_amdgcn_sched_barrier(0);                      // (every load above is in flight before the first add)
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < kCombineBatch; ++k) s += g + k * G < nblk ? pv[k] : 0.0;
+  for (int b0 = g + kCombineBatch * G; b0 < nblk; b0 += kCombineBatch * G) {
+#pragma unroll
+    for (int k = 0; k < kCombineBatch; ++k) {
+      const int b = b0 + k * G;
+      pv[k] = p[(size_t)(b < nblk ? b : nblk - 1) * bstride];
+    }
+#pragma unroll
+    for (int k = 0; k < kCombineBatch; ++k) s += b0 + k * G < nblk ? pv[k] : 0.0;
+  }
+  if (g < G) sw[g][n] = s;
   __syncthreads();
   if ((int)threadIdx.x < PB) {
-    double s = sw[0][threadIdx.x];
+    double a = sw[0][threadIdx.x];
 #pragma unroll
-    for (int q = 1; q < G; ++q) s += sw[q][threadIdx.x];
-    w[threadIdx.x] = s;
+    for (int q = 1; q < G; ++q) a += sw[q][threadIdx.x];
+    w[threadIdx.x] = a;
+  }
+  __syncthreads();
+  if (g < NCH) {                                          // (sw is free again: its readers are past the barrier)
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int col = g * CH + k;
+      if (col < PB) a = __builtin_fma((double)c[k >> 2][k & 3], w[col], a);
+    }
+    sw[g][n] = a;
   }
   __syncthreads();
   if ((int)threadIdx.x < PB) {
     const int m = threadIdx.x;
-    double s = 0.0;
-#pragma unroll 8
-    for (int k = 0; k < PB; ++k) s = __builtin_fma((double)coef[m * PB + k], w[k], s);
-    U[((size_t)jj * T + t) * PB + m] = (float)((double)scale * s);
+    double a = sw[0][m];
+#pragma unroll
+    for (int q = 1; q < NCH; ++q) a += sw[q][m];
+    U[((size_t)jj * T + t) * PB + m] = (float)((double)scale * a);
   }
 }
 
 // (c) out_it = sum_j sum_m T_m(x_ij) U[j][t][m] + noise v_it on this rank's rows [r0, r1); noise v_it (or 0) elsewhere.
-// A workgroup: 64 rows x 4 groups of projections (group g takes jj = g, g + 4, ...), the groups' sums added in order.
+// A workgroup: 64 rows x 4 groups of projections (wave g takes jj = g, g + 4, ...), the groups' sums added in order.
+// Every global load is requested before the first wait, in this order: the lane's coordinates (unconditional, on a row clamped
+// into this rank's slice and into [0, N - 1], behind the wave-uniform jj < jn only), wave 0's V[o] for the noise term, then the
+// thread's share of U as dwordx4 loads (at most kTrips, a wave whose share lies past jn PB skips the trip).  Then U goes to
+// LDS, one barrier, and the Clenshaw sums.  A row outside the slice computes on a clamped coordinate and is replaced by 0
+// at the end; V[o] is read by the thread that later writes out[o], so out may alias V.
+// (The dwordx4 loads of U are 16-byte aligned when the caller's workspace is, as hipMalloc's and torch's are: U lies a
+// multiple of 64 bytes behind it.  Behind an 8-byte aligned workspace they are unaligned loads, which gfx950 serves.)
 // grid (row blocks of 64, T)
 template <int PB>
 __global__ __launch_bounds__(256) void lr_output_kernel(const float *__restrict__ xt, const float *__restrict__ U,
                                                         const float *__restrict__ V, float *__restrict__ out, int N, int T,
                                                         int j0, int jn, int r0, int r1, float noise) {
-  __shared__ float su[kPrepMaxJ * PB];
+  __shared__ __attribute__((aligned(16))) float su[kPrepMaxJ * PB];
   __shared__ float sacc[4][kOutRows];
   const int t = blockIdx.y;
-  for (int e = threadIdx.x; e < jn * PB; e += 256) su[e] = U[((size_t)(e / PB) * T + t) * PB + e % PB];
-  __syncthreads();
-  const int r = threadIdx.x & (kOutRows - 1), g = threadIdx.x / kOutRows;
+  const int r = threadIdx.x & (kOutRows - 1), g = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
   const int i = blockIdx.x * kOutRows + r;
   const bool mine = i >= r0 && i < r1;
+  int ic = i > r0 ? i : r0;
+  ic = ic < r1 ? ic : r1 - 1;
+  ic = ic < N ? ic : N - 1;
+  ic = ic > 0 ? ic : 0;
   constexpr int kMaxPer = kPrepMaxJ / 4;
   float xv[kMaxPer];
 #pragma unroll
-  for (int q = 0; q < kMaxPer; ++q) {                     // this lane's coordinates, requested together
+  for (int q = 0; q < kMaxPer; ++q) {
     const int jj = g + 4 * q;
-    xv[q] = (mine && jj < jn) ? xt[(size_t)(j0 + jj) * N + i] : 0.f;
+    xv[q] = jj < jn ? xt[(size_t)(j0 + jj) * N + ic] : 0.f;
   }
+  float vn = 0.f;
+  if (g == 0 && noise != 0.f) vn = V[(size_t)(i < N ? i : N - 1) * T + t];
+  constexpr int kTrips = (kPrepMaxJ * PB / 4 + 255) / 256;
+  const int nu4 = jn * (PB / 4);                          // U[.][t][.] of the jn projections as float4
+  float4v uv[kTrips];
+#pragma unroll
+  for (int k = 0; k < kTrips; ++k)
+    if (g * kOutRows + 256 * k < nu4) {
+      const int e = (int)threadIdx.x + 256 * k, ec = e < nu4 ? e : nu4 - 1;
+      uv[k] = *reinterpret_cast<const float4v *>(U + ((size_t)(ec / (PB / 4)) * T + t) * PB + 4 * (ec % (PB / 4)));
+    }
+  __builtin_amdgcn_sched_barrier(0);                      // (every load above is in flight before the first wait)
+#pragma unroll
+  for (int k = 0; k < kTrips; ++k)
+    if (g * kOutRows + 256 * k < nu4) {
+      const int e = (int)threadIdx.x + 256 * k;
+      if (e < nu4) *reinterpret_cast<float4v *>(su + 4 * e) = uv[k];
+    }
+  __syncthreads();
   float acc = 0.f;
 #pragma unroll
   for (int q = 0; q < kMaxPer; ++q) {
@@ -333,10 +411,9 @@ __global__ __launch_bounds__(256) void lr_output_kernel(const float *__restrict_
   sacc[g][r] = acc;
   __syncthreads();
   if (g != 0 || i >= N) return;
-  const size_t o = (size_t)i * T + t;
   float res = mine ? (sacc[0][r] + sacc[1][r]) + (sacc[2][r] + sacc[3][r]) : 0.f;
-  if (noise != 0.f) res = __builtin_fmaf(noise, V[o], res);
-  out[o] = res;
+  if (noise != 0.f) res = __builtin_fmaf(noise, vn, res);
+  out[(size_t)i * T + t] = res;
 }
 
 template <int PB>
