@@ -204,6 +204,29 @@ int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, c
                                    void *stream);
 
 /*
+ * The same two kernels for a LIST of columns of Z under one form and with a factor per column (kernels with one lengthscale and
+ * one weight per projection: the columns are served in classes, each with its own inv_w, G, p and r).  For c < nc, j = cols[c]
+ * and x_ic = (Z[i ldz + j] - mid[c]) * inv_w:
+ *   rpgp_lowrank_features_cols_f64: B[i ldb + c r + k] = col_scale[c] * sum_{m < p} T_m(x_ic) G[m r + k];
+ *   rpgp_lowrank_features_grad_cols_f64: gZ[i ldg + cols[c]] = col_scale[c] * inv_w * sum_{m < p} T_m(x_ic) sum_{k < r}
+ *     Gd[m r + k] W[i, c r + k],  W = ca alpha v^T + cy Y on the nc r columns of this form.
+ * cols (int32), mid and col_scale (float64) are device arrays of length nc; cols holds distinct indices in [0, ldz) in any order
+ * (the caller's contract: they are not read on the host).  B, Y and v point at the form's first feature column, so the kernels
+ * see a dense nc r block: the columns of B outside [0, nc r) and the columns of gZ that are not listed are not touched.  The
+ * adjoint's factor is the double product col_scale[c] * inv_w; with cols = 0 ... J - 1, ldz = J and col_scale = sqrt_scale both
+ * return the bits of rpgp_lowrank_features_f64 / rpgp_lowrank_features_grad_f64.  Float64 throughout, fixed order, no atomics:
+ * repeated calls are bit-identical.  Limits: N >= 1, 1 <= nc <= 64, 1 <= r <= p <= 128, ldb, ldy >= nc r, ldz, ldg >= nc (and
+ * > max(cols)).
+ */
+int rpgp_lowrank_features_cols_f64(const double *Z, int64_t N, int nc, int ldz, const int32_t *cols, const double *mid,
+                                   double inv_w, const double *G, int p, int r, const double *col_scale, double *B, int64_t ldb,
+                                   void *stream);
+int rpgp_lowrank_features_grad_cols_f64(const double *Z, int64_t N, int nc, int ldz, const int32_t *cols, const double *mid,
+                                        double inv_w, const double *Gd, int p, int r, const double *col_scale, const double *Y,
+                                        int64_t ldy, const double *alpha, const double *v, double ca, double cy, double *gZ,
+                                        int64_t ldg, void *stream);
+
+/*
  * Rectangular fused MVM:  out = scale * sum_j K_j(Z1,Z2) @ V      (Z1: M x ., Z2: N x ., V: N x T, out: M x T)
  * Replaces K(X*,X) @ alpha and K(X,X*) blocks of the prediction strategy driven from training_routines.py:551-575.
  */

@@ -59,6 +59,9 @@ SIGNATURES = {
     "rpgp_lowrank_features_f64": (_int, [_vp, _i64, _int, _int, _vp, _f64, _vp, _int, _int, _f64, _vp, _i64, _vp]),
     "rpgp_lowrank_features_grad_f64": (_int, [_vp, _i64, _int, _int, _vp, _f64, _vp, _int, _int, _f64, _vp, _i64, _vp, _vp,
                                                _f64, _f64, _vp, _i64, _vp]),
+    "rpgp_lowrank_features_cols_f64": (_int, [_vp, _i64, _int, _int, _vp, _vp, _f64, _vp, _int, _int, _vp, _vp, _i64, _vp]),
+    "rpgp_lowrank_features_grad_cols_f64": (_int, [_vp, _i64, _int, _int, _vp, _vp, _f64, _vp, _int, _int, _vp, _vp, _i64,
+                                                    _vp, _vp, _f64, _f64, _vp, _i64, _vp]),
     "rpgp_mvm_rect_workspace_bytes": (_sz, [_i64, _i64, _int]),
     "rpgp_mvm_rect": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
     "rpgp_dense": (_int, [_vp, _vp, _vp, _i64, _i64, _int, _int, _i64, _int, _int, _f32, _vp]),

@@ -20,6 +20,8 @@ class HipBackend:
     lowrank_post_select = staticmethod(ops.lowrank_post_select)
     lowrank_features = staticmethod(ops.lowrank_features)
     lowrank_features_grad = staticmethod(ops.lowrank_features_grad)
+    lowrank_features_cols = staticmethod(ops.lowrank_features_cols)
+    lowrank_features_grad_cols = staticmethod(ops.lowrank_features_grad_cols)
     mvm_rect = staticmethod(ops.mvm_rect)
     dense = staticmethod(ops.dense)
     bilinear_grad = staticmethod(ops.bilinear_grad)

@@ -845,10 +845,19 @@ struct FeatLane {
 // multiplies it by G's column tiles of 16 on v_mfma_f64_16x16x4_f64 (A[row l&15][k l>>4], B[k l>>4][col l&15]; D col l&15,
 // row (l>>4) + 4 reg).  Each product tile whose column is below r goes to the epilogue: init once, then per projection begin,
 // tile per column tile, end.  PB <= 64: G in static LDS, PB x kFeatLd doubles, all 64 columns staged; above: stage_wide.
-template <int PB, typename Epilogue>
+// which column of Z projection j reads: j itself, or the entry j of a list (the *_cols kernels)
+struct ColsAll {
+  __device__ __forceinline__ int operator()(int j) const { return j; }
+};
+struct ColsList {
+  const int *__restrict__ cols;
+  __device__ __forceinline__ int operator()(int j) const { return cols[j]; }
+};
+
+template <int PB, typename Epilogue, typename Cols = ColsAll>
 __device__ __forceinline__ void lr_features_body(const double *__restrict__ Z, long long N, int J, int ldz,
                                                  const double *__restrict__ mid, double inv_w, const double *__restrict__ G,
-                                                 int p, int r, Epilogue ep) {
+                                                 int p, int r, Epilogue ep, Cols zcol = {}) {
   const int nct = (r + 15) >> 4;
   double *gs;
   int ld;
@@ -874,10 +883,10 @@ __device__ __forceinline__ void lr_features_body(const double *__restrict__ Z, l
   const double *gl = gs + L.kq * ld + L.c16;
   ep.init(L);
   for (int j = 0; j < J; ++j) {
-    const double x = ok ? (Z[row * ldz + j] - mid[j]) * inv_w : 0.0;
+    const double x = ok ? (Z[row * ldz + zcol(j)] - mid[j]) * inv_w : 0.0;
     double a[PB / 4];
     chebyshev_tile<PB>(x, L.kq, a);
-    ep.begin();
+    ep.begin(j);
     for (int ct = 0; ct < nct; ++ct) {
       double4v acc = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
@@ -896,7 +905,7 @@ struct FeatStore {
   double *__restrict__ B;
   long long ldb;
   __device__ __forceinline__ void init(const FeatLane &) {}
-  __device__ __forceinline__ void begin() {}
+  __device__ __forceinline__ void begin(int) {}
   __device__ __forceinline__ void tile(const FeatLane &L, int j, int col, const double4v &acc) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -904,6 +913,16 @@ struct FeatStore {
       if (ro < L.N) B[ro * ldb + (long long)j * L.r + col] = sqrt_scale * acc[i];
     }
   }
+  __device__ __forceinline__ void end(const FeatLane &, int) {}
+};
+
+// FeatStore with the factor of projection j read from col_scale[j]
+struct FeatStoreCols {
+  const double *__restrict__ col_scale;
+  FeatStore s;
+  __device__ __forceinline__ void init(const FeatLane &L) { s.init(L); }
+  __device__ __forceinline__ void begin(int j) { s.sqrt_scale = col_scale[j]; }
+  __device__ __forceinline__ void tile(const FeatLane &L, int j, int col, const double4v &acc) { s.tile(L, j, col, acc); }
   __device__ __forceinline__ void end(const FeatLane &, int) {}
 };
 
@@ -926,7 +945,7 @@ struct FeatAdjoint {
       al[i] = ro < L.N ? ca * alpha[ro] : 0.0;
     }
   }
-  __device__ __forceinline__ void begin() {
+  __device__ __forceinline__ void begin(int) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) part[i] = 0.0;
   }
@@ -957,6 +976,21 @@ struct FeatAdjoint {
   }
 };
 
+// FeatAdjoint with the factor col_scale[j] * inv_w per projection, written to column cols[j] of gZ (W's columns stay j r + k)
+struct FeatAdjointCols {
+  const double *__restrict__ col_scale;
+  const int *__restrict__ cols;
+  double inv_w;
+  FeatAdjoint a;
+  __device__ __forceinline__ void init(const FeatLane &L) { a.init(L); }
+  __device__ __forceinline__ void begin(int j) {
+    a.fac = col_scale[j] * inv_w;
+    a.begin(j);
+  }
+  __device__ __forceinline__ void tile(const FeatLane &L, int j, int col, const double4v &acc) { a.tile(L, j, col, acc); }
+  __device__ __forceinline__ void end(const FeatLane &L, int j) { a.end(L, cols[j]); }
+};
+
 // B[i ldb + j r + k] = sqrt_scale * sum_{m < p} T_m(x_ij) G[m r + k],  x_ij = (Z[i ldz + j] - mid[j]) inv_w.
 // grid (ceil(N / 64)); PB > 64: dynamic LDS wide_lds_bytes(PB, ceil(r / 16))
 template <int PB>
@@ -978,6 +1012,29 @@ __global__ __launch_bounds__(256) void lr_features_grad_kernel(const double *__r
                                                                const double *__restrict__ alpha, const double *__restrict__ v,
                                                                double ca, double cy, double *__restrict__ gZ, long long ldg) {
   lr_features_body<PB>(Z, N, J, ldz, mid, inv_w, Gd, p, r, FeatAdjoint{fac, Y, ldy, alpha, v, ca, cy, gZ, ldg});
+}
+
+// The two kernels on a list of columns under one form, with a factor per column (rpgp_lowrank_features_cols_f64 /
+// rpgp_lowrank_features_grad_cols_f64): the same body; projection c reads column cols[c] of Z, B / Y / v are the form's dense
+// nc r block, gZ is written at column cols[c].  Same grid and LDS as the kernels above.
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_cols_kernel(const double *__restrict__ Z, long long N, int nc, int ldz,
+                                                               const int *__restrict__ cols, const double *__restrict__ mid,
+                                                               double inv_w, const double *__restrict__ G, int p, int r,
+                                                               const double *__restrict__ col_scale, double *__restrict__ B,
+                                                               long long ldb) {
+  lr_features_body<PB>(Z, N, nc, ldz, mid, inv_w, G, p, r, FeatStoreCols{col_scale, FeatStore{0.0, B, ldb}}, ColsList{cols});
+}
+
+template <int PB>
+__global__ __launch_bounds__(256) void lr_features_grad_cols_kernel(
+    const double *__restrict__ Z, long long N, int nc, int ldz, const int *__restrict__ cols, const double *__restrict__ mid,
+    double inv_w, const double *__restrict__ Gd, int p, int r, const double *__restrict__ col_scale,
+    const double *__restrict__ Y, long long ldy, const double *__restrict__ alpha, const double *__restrict__ v, double ca,
+    double cy, double *__restrict__ gZ, long long ldg) {
+  lr_features_body<PB>(Z, N, nc, ldz, mid, inv_w, Gd, p, r,
+                       FeatAdjointCols{col_scale, cols, inv_w, FeatAdjoint{0.0, Y, ldy, alpha, v, ca, cy, gZ, ldg}},
+                       ColsList{cols});
 }
 
 // launch of either feature kernel: no dynamic LDS up to PB 64; above 64 KB it needs the function attribute (set per call: it
@@ -1269,6 +1326,36 @@ int rpgp_lowrank_features_grad_f64(const double *Z, int64_t N, int J, int ldz, c
   return dispatch_pb<kFeatMaxRank>(pad8(p), [&](auto pb) {
     return launch_features(lr_features_grad_kernel<decltype(pb)::value>, pb, r, grid, st, Z, (long long)N, J, ldz, mid, inv_w,
                            Gd, p, r, fac, Y, (long long)ldy, alpha, v, ca, cy, gZ, (long long)ldg);
+  });
+}
+
+int rpgp_lowrank_features_cols_f64(const double *Z, int64_t N, int nc, int ldz, const int32_t *cols, const double *mid,
+                                   double inv_w, const double *G, int p, int r, const double *col_scale, double *B, int64_t ldb,
+                                   void *stream) {
+  if (!Z || !cols || !mid || !G || !col_scale || !B || N < 1 || nc < 1 || nc > kPrepMaxJ || ldz < nc || p < 1 ||
+      p > kFeatMaxRank || r < 1 || r > p || ldb < (int64_t)nc * r || N > ((int64_t)1 << 36))
+    return RPGP_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
+  return dispatch_pb<kFeatMaxRank>(pad8(p), [&](auto pb) {
+    return launch_features(lr_features_cols_kernel<decltype(pb)::value>, pb, r, grid, st, Z, (long long)N, nc, ldz,
+                           (const int *)cols, mid, inv_w, G, p, r, col_scale, B, (long long)ldb);
+  });
+}
+
+int rpgp_lowrank_features_grad_cols_f64(const double *Z, int64_t N, int nc, int ldz, const int32_t *cols, const double *mid,
+                                        double inv_w, const double *Gd, int p, int r, const double *col_scale, const double *Y,
+                                        int64_t ldy, const double *alpha, const double *v, double ca, double cy, double *gZ,
+                                        int64_t ldg, void *stream) {
+  if (!Z || !cols || !mid || !Gd || !col_scale || !Y || !alpha || !v || !gZ || N < 1 || nc < 1 || nc > kPrepMaxJ ||
+      ldz < nc || p < 1 || p > kFeatMaxRank || r < 1 || r > p || ldy < (int64_t)nc * r || ldg < nc || N > ((int64_t)1 << 36))
+    return RPGP_EINVAL;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)((N + kFeatRows - 1) / kFeatRows));
+  return dispatch_pb<kFeatMaxRank>(pad8(p), [&](auto pb) {
+    return launch_features(lr_features_grad_cols_kernel<decltype(pb)::value>, pb, r, grid, st, Z, (long long)N, nc, ldz,
+                           (const int *)cols, mid, inv_w, Gd, p, r, col_scale, Y, (long long)ldy, alpha, v, ca, cy, gZ,
+                           (long long)ldg);
   });
 }
 

@@ -190,7 +190,7 @@ class InvQuadLogDet(torch.autograd.Function):
             return _row_sharded_backward(ctx, g_inv_quad, g_logdet)
         elif ctx.mode == "features":
             from . import lowrank_mll
-            gZ, gs, gn, gr = lowrank_mll.backward(ctx, g_inv_quad, g_logdet)
+            gZ, gs, gn, gr, gw = lowrank_mll.backward(ctx, g_inv_quad, g_logdet)
         else:
             probe_solves, probes, alpha = ctx.saved_tensors
             p = ctx.num_probes

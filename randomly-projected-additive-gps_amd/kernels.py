@@ -318,6 +318,21 @@ class GeneralizedProjectionKernel(Kernel):
     def project(self, x):
         return _Project.apply(x.contiguous(), self.effective_projection())
 
+    def float64_operator(self, x1, x2, outputscale):
+        """The float64 FamilyAdditiveOperator of a float32 model at its hyper-parameters exactly as the model holds them
+        (lengthscales, component weights and outputscale = float32 softplus values, widened); x2 None = the symmetric
+        train-train operator.  Served for 1-D RBF sub-kernels without grid interpolation (what the closed-form posterior of
+        lowrank_posterior.py is built on); None otherwise."""
+        if self.ski or self.kernel_type != "RBF" or self.k != 1:
+            return None
+        Peff = (self.projection_module.weight.detach().t().double() /
+                self.lengthscales.detach().reshape(1, -1).double()).contiguous()
+        be = _backend.get_backend()
+        z1 = be.project(x1.detach().double().contiguous(), Peff)
+        z2 = None if x2 is None else be.project(x2.detach().double().contiguous(), Peff)
+        return FamilyAdditiveOperator(z1, z2, outputscale=outputscale.detach().double(),
+                                      comp_weights=self.outputscales.detach().double(), kind="RBF", group=1)
+
     def forward(self, x1, x2, outputscale=None, shard=None, **params):
         same = x2 is None or x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
         z1 = self.project(x1)
@@ -403,10 +418,14 @@ class ScaleKernel(Kernel):
     def forward(self, x1, x2, **params):
         return self.base_kernel.forward(x1, x2, outputscale=self.outputscale, shard=self.shard, **params)
 
-    def float64_operator(self, x1, x2=None):
-        """float64 twin of the operator on (x1, x2) (see ScaledProjectionKernel.float64_operator), or None."""
+    def float64_operator(self, x1, x2=None, weighted=False):
+        """float64 twin of the operator on (x1, x2) (see ScaledProjectionKernel.float64_operator), or None.  The twin of a
+        kernel with per-component weights (GeneralizedProjectionKernel) is given out only to a caller that asks for it
+        (`weighted`: the closed-form posterior); the mixed-precision refinement keeps to the plain operator."""
         f = getattr(self.base_kernel, "float64_operator", None)
         if f is None or (self.shard is not None and getattr(self.shard, "world_size", 1) > 1):
+            return None
+        if isinstance(self.base_kernel, GeneralizedProjectionKernel) and not weighted:
             return None
         return f(x1, x2, self.outputscale)
 

@@ -12,7 +12,12 @@ whose posterior needs no N x N object.  With M = sigma^2 I + B^T B = L L^T (F x 
 and the noisy log-density at any inputs (B* = B at the training inputs) by Woodbury and the determinant lemma in F x F:
     Sigma* + sigma^2 I = sigma^2 (I + B* M^-1 B*^T),   (...)^-1 = (I - B* P^-1 B*^T) / sigma^2,   P = M + B*^T B*,
     log|Sigma* + sigma^2 I| = m log sigma^2 + log|P| - log|M|.
-Everything runs in float64; the accuracy is set by the per-entry tail of the truncation alone (no CG tolerance)."""
+Everything runs in float64; the accuracy is set by the per-entry tail of the truncation alone (no CG tolerance).
+
+A kernel with one lengthscale and one weight per projection (GeneralizedProjectionKernel with RBF sub-kernels and k = 1:
+K = s sum_c w_c exp(-(z_c - z'_c)^2 / 2)) is the same feature model on column forms (column_forms): its columns are put into
+up to MAX_FORMS classes by half-width, each class with the form of its widest column; B is class-major, the columns of component
+c carry the factor sqrt(s w_c) (rpgp_lowrank_features_cols_f64), and F = sum_g nc_g r_g."""
 import math
 
 import torch
@@ -36,6 +41,7 @@ def tail_tolerance(N, outputscale, noise):
         return TAIL_TOL
     return min(TAIL_TOL, max(TAIL_FLOOR, REL_ACCURACY * noise / (N * outputscale)))
 MAX_J = 64
+MAX_FORMS = 4                    # classes of columns with a Chebyshev form each (column_forms)
 MAX_FEATURES = 4096
 MEMORY_SHARE = 0.25              # B (8 N F bytes) may take this share of the device memory
 _PANEL = 4096                    # columns per triangular solve
@@ -58,6 +64,96 @@ class _Form:
         self.kw = rank_cap()[1]                     # the cap this form was selected under goes with it to the kernels
 
 
+class _ColumnForm:
+    """One class of columns and its form: the columns (ascending), their midpoints, the class half-width with inv_w, ranks,
+    tail and G, and the first of its nc r feature columns in B."""
+
+    def __init__(self, cols, mid, h, p, r, tail, G, f0):
+        self.cols, self.mid, self.h, self.p, self.r, self.tail, self.G, self.f0 = cols, mid, h, p, r, tail, G, f0
+        self.inv_w = KAPPA / h if h > 0.0 else 0.0
+        self.f1 = f0 + len(cols) * r
+
+
+class ColumnForms:
+    """The forms of a kernel with one lengthscale and one weight per projection, K = s sum_c w_c exp(-(z_c - z'_c)^2 / 2):
+    up to MAX_FORMS classes of columns by half-width (column_forms), B class-major with class g in columns [f0_g, f1_g)."""
+
+    def __init__(self, classes, cls, comp, weights, scale, tail):
+        self.classes = classes              # the non-empty classes, widest first
+        self.cls = cls                      # class index (into `classes`) of every column
+        self.comp = comp                    # component of every feature column (F, host int64)
+        self.weights, self.scale = weights, scale          # w_c (host float64) and s
+        self.col_scale = (scale * weights).sqrt()          # sqrt(s w_c)
+        self.tail = tail                    # sum_g (sum_{c in g} w_c) tail_g / sum_c w_c
+        self.kw = rank_cap()[1]
+        self.F = classes[-1].f1
+        self.p = max(c.p for c in classes)
+        self.r = max(c.r for c in classes)
+
+    @property
+    def class_ranks(self):
+        """(p, r, columns) of every class."""
+        return [(c.p, c.r, len(c.cols)) for c in self.classes]
+
+    def features(self, be, Z):
+        """B (rows of Z x F, float64): one launch per class, each into its own columns."""
+        B = torch.empty((Z.shape[0], self.F), dtype=torch.float64, device=Z.device)
+        for c in self.classes:
+            be.lowrank_features_cols(Z, c.cols, c.mid, c.inv_w, c.G, self.col_scale[c.cols], out=B[:, c.f0:c.f1], **self.kw)
+        return B
+
+
+def column_classes(hj):
+    """Class of every column from its half-width h_j (a sequence of host floats): min(MAX_FORMS - 1, floor(log2(h_max / h_j)));
+    a column with h_j = 0 joins the last non-empty class; h_max = 0 is one class."""
+    hmax = max(hj)
+    if not hmax > 0.0:
+        return [0] * len(hj)
+    cls = [min(MAX_FORMS - 1, int(math.floor(math.log2(hmax / h)))) if h > 0.0 else -1 for h in hj]
+    last = max(cls)
+    return [last if c < 0 else c for c in cls]
+
+
+def column_forms(be, Z, zmin, zmax, weights, scale, noise):
+    """(ColumnForms, None) for N x J coordinates Z with the column ranges [zmin, zmax], component weights w (J) and outputscale
+    s, or (None, reason).  Every class takes the form of its widest column, selected at the tolerance of the whole kernel
+    (tail_tolerance(N, s sum_c w_c, sigma^2)): a column that needs few Chebyshev terms no longer pays for the widest one."""
+    N, J = Z.shape
+    w = torch.as_tensor(weights, dtype=torch.float64).detach().reshape(-1).cpu()
+    half = (0.5 * (zmax - zmin)).double().cpu()
+    mid_all = (0.5 * (zmin + zmax)).double()
+    hj = (KAPPA * half).tolist()
+    cls = column_classes(hj)
+    cap = rank_cap()[0]
+    tol = tail_tolerance(N, scale * float(w.sum()), noise)
+    classes, index, f0 = [], {}, 0
+    comp = []
+    for g in sorted(set(cls)):
+        cols = [j for j in range(J) if cls[j] == g]
+        h = max(hj[j] for j in cols) * (1.0 + 2.0 ** -20)
+        p, r, tail, G = be.lowrank_post_select(h, tol, cap)
+        if p == 0:
+            return None, "half-width %.3g needs a Chebyshev rank above %d" % (h, cap)
+        index[g] = len(classes)
+        classes.append(_ColumnForm(cols, mid_all[cols].contiguous(), h, p, r, tail, G, f0))
+        f0 = classes[-1].f1
+        for j in cols:
+            comp.extend([j] * r)
+    tail = sum(float(w[c.cols].sum()) * c.tail for c in classes) / float(w.sum())
+    forms = ColumnForms(classes, [index[g] for g in cls], torch.tensor(comp, dtype=torch.int64), w, scale, tail)
+    return forms, None
+
+
+def size_reason(N, F, device, copies, what):
+    """Why N x F features are not served (None when they are): MAX_FEATURES and `copies` N x F float64 matrices within
+    MEMORY_SHARE of the device memory."""
+    if F > MAX_FEATURES:
+        return "%d features exceed %d" % (F, MAX_FEATURES)
+    if device.type == "cuda" and 8.0 * copies * N * F > MEMORY_SHARE * torch.cuda.get_device_properties(device).total_memory:
+        return "the %d x %d %s exceed %.0f%% of the device memory" % (N, F, what, 100 * MEMORY_SHARE)
+    return None
+
+
 class LowrankPosterior:
     """The closed-form feature posterior of one prediction strategy.  Construct with `LowrankPosterior.build(strategy)`,
     which returns (posterior or None, reason)."""
@@ -71,6 +167,7 @@ class LowrankPosterior:
         self.zmin = op64.Z1.min(0).values
         self.zmax = op64.Z1.max(0).values
         self.Z = op64.Z1
+        self.weights = self._weights(op64)
         self.rebuilds = 0
         self._set(form, B, M, L, w)
 
@@ -82,9 +179,16 @@ class LowrankPosterior:
         return mid, h
 
     @staticmethod
-    def _form(be, Z, zmin, zmax, scale, noise):
-        """(form, None) for the interval of [zmin, zmax], or (None, reason)."""
+    def _form(be, Z, zmin, zmax, scale, noise, weights=None):
+        """(form, None) for the interval of [zmin, zmax], or (None, reason).  `weights` (one per column: the kernel has a
+        weight and a lengthscale per projection) selects the column forms."""
         N, J = Z.shape
+        if weights is not None:
+            form, why = column_forms(be, Z, zmin, zmax, weights, scale, noise)
+            if form is None:
+                return None, why
+            why = size_reason(N, form.F, Z.device, 1, "features")
+            return (None, why) if why else (form, None)
         mid, h = LowrankPosterior._interval(zmin, zmax)
         cap = rank_cap()[0]
         p, r, tail, G = be.lowrank_post_select(h, tail_tolerance(N, scale * J, noise), cap)
@@ -98,9 +202,16 @@ class LowrankPosterior:
         return _Form(mid, h, p, r, tail, G), None
 
     @staticmethod
+    def _evaluate(be, Z, form, scale):
+        """B of `form` at the coordinates Z."""
+        if isinstance(form, ColumnForms):
+            return form.features(be, Z)
+        return be.lowrank_features(Z, form.mid, form.inv_w, form.G, scale, **form.kw)
+
+    @staticmethod
     def _factor(be, Z, form, scale, noise, r64):
         """(B, M, L, w) of one form, or None when M = sigma^2 I + B^T B does not factor."""
-        B = be.lowrank_features(Z, form.mid, form.inv_w, form.G, scale, **form.kw)
+        B = LowrankPosterior._evaluate(be, Z, form, scale)
         M = B.t() @ B
         M.diagonal().add_(noise)
         L, info = torch.linalg.cholesky_ex(M)
@@ -121,17 +232,21 @@ class LowrankPosterior:
         if not ops.lowrank_enabled():
             return None, "the low-rank form is switched off (RPGP_LOWRANK=0 or RPGP_FACT_ASM)"
         be = _backend.get_backend()
-        if getattr(be, "lowrank_post_select", None) is None or getattr(be, "lowrank_features", None) is None:
+        if getattr(be, "lowrank_post_select", None) is None:
             return None, "the backend has no low-rank features"
-        f64 = getattr(cm, "float64_operator", None)
-        op64 = f64(x) if f64 is not None else None
+        op64 = cls._float64_operator(cm, x)
         if op64 is None:
-            return None, "the kernel has no float64 form (grid interpolation, family kernel, k > 1 or memory-efficient)"
+            return None, "the kernel has no float64 form (grid interpolation, non-RBF kind, k > 1 or memory-efficient)"
         Z = op64.Z1
         if Z.shape[1] > MAX_J:
             return None, "J = %d exceeds %d" % (Z.shape[1], MAX_J)
+        weights = cls._weights(op64)
+        if getattr(be, "lowrank_features" if weights is None else "lowrank_features_cols", None) is None:
+            return None, "the backend has no low-rank features"
+        if weights is not None and not bool((weights > 0.0).all()):
+            return None, "a component weight is not positive"
         noise = host_float(strategy.noise)
-        form, why = cls._form(be, Z, Z.min(0).values, Z.max(0).values, float(op64._scale), noise)
+        form, why = cls._form(be, Z, Z.min(0).values, Z.max(0).values, float(op64._scale), noise, weights)
         if form is None:
             return None, why
         r64 = cls._residual(strategy)
@@ -139,6 +254,20 @@ class LowrankPosterior:
         if fac is None:
             return None, "sigma^2 I + B^T B is not positive definite"
         return cls(strategy, op64, form, *fac), None
+
+    @staticmethod
+    def _float64_operator(cm, x):
+        """The float64 twin of the model's kernel on x, the kinds with per-component weights included."""
+        f64 = getattr(cm, "float64_operator", None)
+        if f64 is None:
+            return None
+        return f64(x, weighted=True)
+
+    @staticmethod
+    def _weights(op64):
+        """The component weights of the float64 operator on the host (None: the unweighted operator, one shared form)."""
+        w = getattr(op64, "comp_weights", None)
+        return None if w is None else w.detach().double().reshape(-1).cpu()
 
     @staticmethod
     def _residual(strategy):
@@ -156,26 +285,38 @@ class LowrankPosterior:
 
     @property
     def ranks(self):
-        """(p, r, F) of the current form."""
+        """(p, r, F) of the current form; with column forms the largest p and r (`class_ranks` has every class)."""
         return self.form.p, self.form.r, self.B.shape[1]
+
+    @property
+    def class_ranks(self):
+        """[(p, r, columns)] per class of columns (one entry for the shared form)."""
+        if isinstance(self.form, ColumnForms):
+            return self.form.class_ranks
+        return [(self.form.p, self.form.r, self.Z.shape[1])]
 
     # ---- features at other inputs --------------------------------------------------------------------------------------
     def _test_coordinates(self, xs):
-        return self.model.covar_module.float64_operator(xs).Z1
+        return self._float64_operator(self.model.covar_module, xs).Z1
 
     def _features(self, Zs):
         """B* for projected test coordinates, or None (with strategy.lowrank_fallback_reason set) when the interval that
         covers them is not served.  A coordinate outside the interval rebuilds the form once on the union of the ranges."""
         f = self.form
         be = _backend.get_backend()
-        if f.inv_w > 0.0:
+        if isinstance(f, ColumnForms):
+            bad = [(((Zs[:, c.cols] - c.mid) * c.inv_w).abs() > 1.0).any() if c.inv_w > 0.0 else
+                   ((Zs[:, c.cols].min(0).values < self.zmin[c.cols]) | (Zs[:, c.cols].max(0).values > self.zmax[c.cols])).any()
+                   for c in f.classes]
+            outside = bool(torch.stack(bad).any())
+        elif f.inv_w > 0.0:
             outside = bool((((Zs - f.mid) * f.inv_w).abs() > 1.0).any())
         else:
             outside = bool(((Zs.min(0).values < self.zmin) | (Zs.max(0).values > self.zmax)).any())
         if outside:
             zmin = torch.minimum(self.zmin, Zs.min(0).values)
             zmax = torch.maximum(self.zmax, Zs.max(0).values)
-            form, why = self._form(be, self.Z, zmin, zmax, self.scale, self.noise)
+            form, why = self._form(be, self.Z, zmin, zmax, self.scale, self.noise, self.weights)
             fac = None
             if form is not None:
                 fac = self._factor(be, self.Z, form, self.scale, self.noise, self._residual(self.strategy))
@@ -187,7 +328,7 @@ class LowrankPosterior:
             self.zmin, self.zmax = zmin, zmax
             self._set(form, *fac)
             self.rebuilds += 1
-        return be.lowrank_features(Zs, self.form.mid, self.form.inv_w, self.form.G, self.scale, **self.form.kw)
+        return self._evaluate(be, Zs, self.form, self.scale)
 
     # ---- prediction ----------------------------------------------------------------------------------------------------
     def predict(self, xs, at_train=False):

@@ -435,6 +435,98 @@ def lowrank_features_grad(Z, mid, inv_w, G, scale, Y, alpha, v, ca, cy, out=None
     return out
 
 
+LOWRANK_FEATURE_COLS = 64       # most columns of one rpgp_lowrank_features_cols_f64 / rpgp_lowrank_features_grad_cols_f64 call
+
+
+def _feature_columns(what, Z, cols, mid, col_scale, p, r, max_rank):
+    """The checked arguments of the column-list feature kernels: (cols int32, mid, col_scale) on Z's device.  `cols` is read
+    on the host (a list, or a tensor that is copied there): distinct indices in [0, Z.shape[1]), 1 ... 64 of them."""
+    _check_feature_rank(what, p, max_rank)
+    cl = [int(c) for c in (cols.tolist() if torch.is_tensor(cols) else cols)]
+    nc, ldz = len(cl), Z.shape[1]
+    if Z.shape[0] < 1 or not 1 <= nc <= LOWRANK_FEATURE_COLS or not 1 <= r <= p:
+        raise ValueError("%s: N = %d, %d columns, p = %d, r = %d outside N >= 1, 1 ... %d columns, r <= p <= %d"
+                         % (what, Z.shape[0], nc, p, r, LOWRANK_FEATURE_COLS, max_rank))
+    if len(set(cl)) != nc or min(cl) < 0 or max(cl) >= ldz:
+        raise ValueError("%s: cols must be distinct indices in [0, %d)" % (what, ldz))
+    dev = Z.device
+    cols_t = torch.tensor(cl, dtype=torch.int32).to(dev)
+    mid_t = torch.as_tensor(mid, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+    cs_t = torch.as_tensor(col_scale, dtype=torch.float64).to(dev).reshape(-1).contiguous()
+    if mid_t.numel() != nc or cs_t.numel() != nc:
+        raise ValueError("%s: mid and col_scale must have one entry per listed column" % what)
+    return cols_t, mid_t, cs_t, nc
+
+
+def lowrank_features_cols(Z, cols, mid, inv_w, G, col_scale, out=None, max_rank=64):
+    """B (N x nc r float64) with B[i, c r + k] = col_scale[c] sum_m T_m((Z[i, cols[c]] - mid[c]) inv_w) G[m, k]
+    (rpgp_lowrank_features_cols_f64): the features of the listed columns of Z under ONE form (inv_w, G) and a factor per
+    column.  `out`: an N x nc r float64 view with unit column stride and any row stride (the block of a wider B that belongs
+    to this form; nothing outside it is touched).  ValueError for a repeated or out-of-range column, more than 64 columns,
+    p > max_rank or max_rank > 128: nothing is launched then."""
+    lib = _lib.load()
+    Z = _require(Z, "Z", 2, allow64=True)
+    if Z.dtype != torch.float64:
+        raise TypeError("Z must be float64")
+    N, ldz = Z.shape
+    Gt = torch.as_tensor(G, dtype=torch.float64).to(Z.device).contiguous()
+    if Gt.dim() != 2:
+        raise ValueError("G must be p x r")
+    p, r = Gt.shape
+    cols_t, mid_t, cs_t, nc = _feature_columns("lowrank_features_cols", Z, cols, mid, col_scale, p, r, max_rank)
+    if out is None:
+        out = torch.empty((N, nc * r), dtype=torch.float64, device=Z.device)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (N, nc * r) or (out.stride(1) != 1 and nc * r > 1) or \
+            out.device != Z.device or (N > 1 and out.stride(0) < nc * r):
+        raise ValueError("out must be an N x nc r float64 view with unit column stride")
+    with _on(Z.device):
+        _lib.check(lib.rpgp_lowrank_features_cols_f64(Z.data_ptr(), N, nc, ldz, cols_t.data_ptr(), mid_t.data_ptr(),
+                                                      float(inv_w), Gt.data_ptr(), p, r, cs_t.data_ptr(), out.data_ptr(),
+                                                      max(out.stride(0), nc * r), _stream()),
+                   "rpgp_lowrank_features_cols_f64")
+    return out
+
+
+def lowrank_features_grad_cols(Z, cols, mid, inv_w, G, col_scale, Y, alpha, v, ca, cy, out=None, max_rank=64):
+    """The adjoint of lowrank_features_cols (rpgp_lowrank_features_grad_cols_f64): for dL/dB = W = ca alpha v^T + cy Y on the
+    form's N x nc r block (Y, v: the block's columns of the whole Y and v), out[:, cols[c]] = dL/dZ[:, cols[c]].  `out`: an
+    N x Z.shape[1] float64 view with unit column stride (allocated when None); its columns that are not listed are not touched.
+    Same limits as lowrank_features_cols."""
+    lib = _lib.load()
+    Z = _require(Z, "Z", 2, allow64=True)
+    if Z.dtype != torch.float64:
+        raise TypeError("Z must be float64")
+    N, ldz = Z.shape
+    Gd = chebyshev_derivative(torch.as_tensor(G, dtype=torch.float64).cpu().numpy())
+    if Gd.ndim != 2:
+        raise ValueError("G must be p x r")
+    p, r = Gd.shape
+    cols_t, mid_t, cs_t, nc = _feature_columns("lowrank_features_grad_cols", Z, cols, mid, col_scale, p, r, max_rank)
+    dev = Z.device
+    Gd_t = torch.from_numpy(Gd).to(dev).contiguous()
+    if Y.dtype != torch.float64 or Y.dim() != 2 or Y.shape[0] != N or Y.shape[1] < nc * r or Y.stride(1) != 1 or \
+            Y.device != dev or (N > 1 and Y.stride(0) < nc * r):
+        raise ValueError("Y must be an N x (>= nc r) float64 matrix on Z's device with unit column stride")
+    alpha_t = alpha.reshape(-1)
+    v_t = v.reshape(-1)
+    if alpha_t.dtype != torch.float64 or alpha_t.numel() != N or v_t.dtype != torch.float64 or v_t.numel() != nc * r:
+        raise ValueError("alpha (N) and v (nc r) must be float64")
+    alpha_t, v_t = alpha_t.contiguous(), v_t.contiguous()
+    if out is None:
+        out = torch.empty((N, ldz), dtype=torch.float64, device=dev)
+    elif out.dtype != torch.float64 or tuple(out.shape) != (N, ldz) or out.stride(1) != 1 or out.device != dev or \
+            (N > 1 and out.stride(0) < ldz):
+        raise ValueError("out must be an N x Z.shape[1] float64 view with unit column stride")
+    with _on(dev):
+        _lib.check(lib.rpgp_lowrank_features_grad_cols_f64(Z.data_ptr(), N, nc, ldz, cols_t.data_ptr(), mid_t.data_ptr(),
+                                                           float(inv_w), Gd_t.data_ptr(), p, r, cs_t.data_ptr(), Y.data_ptr(),
+                                                           max(Y.stride(0), nc * r), alpha_t.data_ptr(), v_t.data_ptr(),
+                                                           float(ca), float(cy), out.data_ptr(), max(out.stride(0), ldz),
+                                                           _stream()),
+                   "rpgp_lowrank_features_grad_cols_f64")
+    return out
+
+
 def bilinear_grad_lowrank(plan, L, R, scale, j0=0, j1=None):
     """(gZ [N x J], gscale [scalar tensor]) of bilinear_grad on the plan's Z, from the low-rank form (rpgp_bilinear_grad_lowrank).
     The columns outside [j0, j1) are zero."""

@@ -140,7 +140,9 @@ lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
 # prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
 # with a float64 twin (k = 1, no grid), J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default, up to 128), at most 4096
 # features in 25 % of the device memory gets its posterior mean, covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
-# where it is not served: the prediction strategy as before.
+# where it is not served: the prediction strategy as before.  The weighted kinds (rp_poly / strictly_additive with k = 1 and RBF
+# sub-kernels: one lengthscale and one weight per projection) are served on column forms, up to four classes of columns with a
+# Chebyshev form each (lowrank_posterior.column_forms).
 lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
 # training on the exact marginal likelihood of the same truncated kernel in closed form (lowrank_mll.py): value and full
 # gradient from the explicit features B (K_lr = B B^T) through F x F factorisations in float64: no probes, no CG, no SLQ, the
@@ -148,7 +150,8 @@ lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
 # (AdditiveRPOperator.lowrank_mll_form): an unsharded plain additive-RP RBF operator (k = 1, no grid, not memory-efficient),
 # J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default) at lowrank_posterior's tail tolerance, F < N, F <= 4096, B and B M^-1 in 25 % of the device
 # memory.  Where served it takes precedence over lowrank_kernel and over the Cholesky regime (use_cholesky); where not, the
-# step runs exactly as with the setting off (lowrank_kernel then applies as before).
+# step runs exactly as with the setting off (lowrank_kernel then applies as before).  The weighted kinds (FamilyAdditiveOperator,
+# RBF, k = 1, every weight positive) are served on column forms, with the gradient of every component weight.
 lowrank_mll = _setting("lowrank_mll", False, flag=True)
 
 

@@ -530,6 +530,8 @@ def train_exact_gp(trainX, trainY, testX, testY, kind, model_kwargs, train_kwarg
     restart_check_conv = train_kwargs.pop("rr_check_conv", False)
     restart_kwargs = dict(train_kwargs, max_iter=restart_iters, check_conv=restart_check_conv)
 
+    from . import lowrank_mll, settings
+    served0 = lowrank_mll.served_counts()
     factory = _ExactGPFactory(trainX, trainY, kind, model_kwargs, devices, output_device, dtype)
     if skip_random_restart:
         model, likelihood, mll = factory()
@@ -544,9 +546,16 @@ def train_exact_gp(trainX, trainY, testX, testY, kind, model_kwargs, train_kwarg
     likelihood.eval()
     mll.eval()
     model_metrics = {"trained_epochs": trained_epochs}
+    if settings.lowrank_mll.on():
+        # the share of the fit's objective evaluations that ran in the closed-form features mode
+        served, decided = (b - a for a, b in zip(served0, lowrank_mll.served_counts()))
+        model_metrics["lowrank_mll_share"] = served / decided if decided else 0.0
     evaluated, pred_mean, test_warnings = _evaluate_exact_gp(model, likelihood, mll, trainX, trainY, testX, testY,
                                                              skip_posterior_variances, evaluate_on_train, record_pred_unc)
     model_metrics.update(evaluated)
+    if settings.lowrank_posterior.on():
+        st = getattr(model, "prediction_strategy", None)
+        model_metrics["lowrank_posterior_served"] = int(getattr(st, "lowrank", None) is not None)
     model_metrics["training_warnings"] = len(fit_warnings)
     model_metrics["testing_warning"] = "" if len(test_warnings) == 0 else test_warnings[-1].message
     model_metrics["state_dict_file"] = _save_state_dict(model)

@@ -1,7 +1,10 @@
 """Optimiser-step timing of the exact additive-RP GP with the closed-form features objective (settings.lowrank_mll) against the
 setting off and against settings.lowrank_kernel, on synthetic stand-ins of the BASELINE configs, plus the stages of one
 features-mode evaluation (features, Gram, Cholesky, Y = B M^-1, the adjoint kernel and its read bandwidth, beside the features
-kernel at the same N, J, p, r) and optionally one L-BFGS fit.  Prints, and appends to --out, one JSON line per measurement."""
+kernel at the same N, J, p, r) and optionally one L-BFGS fit.  --weighted builds the weighted rp_poly model (J = 20, k = 1: one
+lengthscale and one weight per projection, served on column forms) with the lengthscales spread --spread times across the
+projections; --max_forms 1 holds it to a single form for comparison.  Prints, and appends to --out, one JSON line per
+measurement."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -18,11 +21,33 @@ def _recording(self, noise=None):
     r = _orig(self, noise)
     _last["served"] = r is not None
     _last["ranks"] = r.ranks if r is not None else None
+    _last["class_ranks"] = getattr(r, "class_ranks", None)
     _last["reason"] = self.lowrank_mll_reason
     return r
 
 
 operators.AdditiveRPOperator.lowrank_mll_form = _recording
+
+
+WEIGHTED = {"on": False, "spread": 1.0}
+
+
+def _weighted_problem(X, y, J, half_width, spread, dev):
+    """The weighted rp_poly model (k = 1): lengthscale of projection j proportional to spread^(j / (J - 1)), scaled so that the
+    widest column has the half-width; the mixing weights as the kernel initialises them."""
+    from rpgp_amd.kernels import inv_softplus
+    model, lik = create_exact_gp(X, y, "rp_poly", J=J, k=1, noise_prior=True, kernel_type="RBF", learn_proj=False,
+                                 weighted=True)
+    model = model.to(dev)
+    kern = model.covar_module.base_kernel
+    with torch.no_grad():
+        ls = torch.tensor([spread ** (j / max(J - 1, 1)) for j in range(J)], dtype=torch.float64, device=dev)
+        Z = (X.double() @ kern.projection_module.weight.double().t()) / ls
+        h0 = KAPPA * float(((Z.max(0).values - Z.min(0).values) * 0.5).max())
+        if half_width is not None:
+            ls = ls * (h0 / half_width)
+        kern.raw_lengthscales.data = inv_softplus(ls).reshape(1, -1).to(kern.raw_lengthscales)
+    return model, lik
 
 
 def _problem(N, d, J, half_width, dev):
@@ -32,6 +57,8 @@ def _problem(N, d, J, half_width, dev):
     y = (y - y.mean()) / y.std()
     X, y = X.to(dev), y.to(dev)
     torch.manual_seed(0)
+    if WEIGHTED["on"]:
+        return _weighted_problem(X, y, J, half_width, WEIGHTED["spread"], dev) + (X, y)
     model, lik = create_exact_gp(X, y, "additive_rp", J=J, noise_prior=True, kernel_type="RBF", learn_proj=False,
                                  prescale=True)
     model = model.to(dev)
@@ -85,11 +112,61 @@ def steps(name, N, d, J, mode, n_steps, warmup, half_width, out):
            "max_rank": settings.lowrank_max_rank.value(), "steps": n_steps, "warmup": warmup, "step_ms_median": 1e3 * st[len(st) // 2], "step_ms_min": 1e3 * st[0],
            "step_ms_max": 1e3 * st[-1], "served_steps": sum(served) if mode == "mll" else None,
            "ranks_pr_F": ranks[-1] if mode == "mll" else None}
+    if WEIGHTED["on"]:
+        res.update(_weighted_tags(), class_ranks_p_r_columns=_last.get("class_ranks") if mode == "mll" else None)
+    _emit(res, out)
+
+
+def _weighted_tags():
+    from rpgp_amd import lowrank_posterior
+    return {"model": "rp_poly weighted k=1", "spread": WEIGHTED["spread"], "max_forms": getattr(lowrank_posterior, "MAX_FORMS", None)}
+
+
+def stages_weighted(name, N, d, J, half_width, out):
+    """The stages of one features-mode evaluation of the weighted model: the feature and adjoint launches of every class
+    (summed), the Gram matrix, its factor and Y = B M^-1."""
+    from rpgp_amd import backend
+    from rpgp_amd.lowrank_posterior import column_forms
+    dev = torch.device("cuda:0")
+    be = backend.get_backend()
+    model, lik, X, y = _problem(N, d, J, half_width, dev)
+    kern = model.covar_module.base_kernel
+    cap = settings.lowrank_max_rank.value()
+    with torch.no_grad():
+        Z = kern.project(X).double().contiguous()
+        s, noise = float(model.covar_module.outputscale), float(lik.noise)
+        forms, why = column_forms(be, Z, Z.min(0).values, Z.max(0).values, kern.outputscales.double(), s, noise)
+        if forms is None:
+            _emit(dict(_weighted_tags(), kind="stages", config=name, N=N, J=J, half_width=half_width, max_rank=cap,
+                       served=False, reason=why), out)
+            return
+        t_feat, B = _timed(lambda: forms.features(be, Z))
+        t_gram, M = _timed(lambda: B.t() @ B)
+        M.diagonal().add_(noise)
+        t_chol, L = _timed(lambda: torch.linalg.cholesky_ex(M)[0])
+        t_minv, Minv = _timed(lambda: torch.cholesky_inverse(L))
+        t_y, Y = _timed(lambda: B @ Minv)
+        alpha = torch.randn(N, 1, dtype=torch.float64, device=dev)
+        v = (B.t() @ alpha).reshape(-1)
+        gZ = torch.empty_like(Z)
+
+        def adjoint():
+            for c in forms.classes:
+                be.lowrank_features_grad_cols(Z, c.cols, c.mid, c.inv_w, c.G, forms.col_scale[c.cols], Y[:, c.f0:c.f1], alpha,
+                                              v[c.f0:c.f1], -1.0, 1.0, out=gZ, **forms.kw)
+            return gZ
+        t_grad, _ = _timed(adjoint)
+    res = dict(_weighted_tags(), kind="stages", config=name, N=N, J=J, p=forms.p, r=forms.r, F=forms.F,
+               class_ranks_p_r_columns=forms.class_ranks, half_width=half_width, max_rank=cap, tail=forms.tail,
+               features_ms=t_feat, gram_ms=t_gram, cholesky_ms=t_chol, cholesky_inverse_ms=t_minv, Y_ms=t_y,
+               grad_kernel_ms=t_grad)
     _emit(res, out)
 
 
 def stages(name, N, d, J, half_width, out):
     """The stages of one features-mode evaluation at the model's first step."""
+    if WEIGHTED["on"]:
+        return stages_weighted(name, N, d, J, half_width, out)
     from rpgp_amd.lowrank_posterior import _Form, LowrankPosterior, tail_tolerance
     dev = torch.device("cuda:0")
     model, lik, X, y = _problem(N, d, J, half_width, dev)
@@ -168,6 +245,8 @@ def lbfgs_fit(name, N, d, J, half_width, max_iter, out):
 
 
 def _emit(res, out):
+    if globals().get("TAG"):
+        res = dict(res, tag=TAG)
     line = json.dumps(res)
     print(line, flush=True)
     if out:
@@ -185,9 +264,18 @@ if __name__ == "__main__":
     ap.add_argument("--stages", action="store_true", help="also time the stages of one features-mode evaluation")
     ap.add_argument("--lbfgs", type=int, default=0, help="also run one L-BFGS fit of at most this many iterations")
     ap.add_argument("--max_rank", type=int, default=64, help="settings.lowrank_max_rank for every measurement (1 ... 128)")
+    ap.add_argument("--weighted", action="store_true", help="the weighted rp_poly model (k = 1) instead of additive_rp")
+    ap.add_argument("--spread", type=float, default=1.0, help="--weighted: longest / shortest lengthscale across projections")
+    ap.add_argument("--max_forms", type=int, default=None, help="--weighted: at most this many column forms (default: 4)")
+    ap.add_argument("--tag", default=None, help="a label copied into every record (which run, which build)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     a = ap.parse_args()
+    TAG = a.tag
     settings.lowrank_max_rank._set(a.max_rank)
+    WEIGHTED.update(on=a.weighted, spread=a.spread)
+    if a.max_forms is not None:
+        from rpgp_amd import lowrank_posterior
+        lowrank_posterior.MAX_FORMS = a.max_forms
     table = {"C4": ("C4 synthetic 50k RPA-GP", 50000, 20, 20),
              "C5X": ("C5-sized exact RPA-GP (synthetic, J=20, no SKI)", 391386, 20, 20)}
     for c in a.configs.split(","):

@@ -1,7 +1,9 @@
 """Prediction with settings.lowrank_posterior on and off (the closed-form posterior of the explicit Chebyshev low-rank features,
 lowrank_posterior.py), on synthetic stand-ins: the stages of the feature posterior (features, Gram, factor, test features,
 solves), the feature kernel's time and write bandwidth, and each prediction mode (full: mean + covariance + test NLL; mean +
-variances + test NLL; mean only) in a warmed process.  One JSON line per record, appended to --out."""
+variances + test NLL; mean only) in a warmed process.  --weighted: the weighted rp_poly model (J = 20, k = 1) with the
+lengthscales spread --spread times across the projections, served on column forms.  One JSON line per record, appended to
+--out."""
 import argparse, json, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -37,6 +39,31 @@ def model_of(N, d, J, n_test, half_width, dev, noise=0.1):
     return model, lik, ExactMarginalLogLikelihood(lik, model), Xs.to(dev), ys.to(dev)
 
 
+def weighted_model_of(N, d, J, n_test, half_width, spread, dev, noise=0.1):
+    """model_of for the weighted rp_poly kernel (k = 1): lengthscale of projection j proportional to spread^(j / (J - 1)),
+    scaled so that the widest column has the half-width."""
+    from rpgp_amd.kernels import PolynomialProjectionKernel, inv_softplus
+    g = torch.Generator().manual_seed(0)
+    X = torch.randn(N, d, generator=g)
+    P = torch.randn(d, J, generator=torch.Generator().manual_seed(1)) / math.sqrt(d)
+    y = torch.sin(X).sum(1) + 0.05 * torch.randn(N, generator=g)
+    y = (y - y.mean()) / y.std()
+    Xs = torch.randn(n_test, d, generator=g) * 0.8
+    ys = torch.sin(Xs).sum(1) / float(torch.sin(X).sum(1).std())
+    ls = torch.tensor([spread ** (j / max(J - 1, 1)) for j in range(J)])
+    if half_width is not None:
+        Z = (X @ P) / ls
+        ls = ls * (KAPPA * float(((Z.max(0).values - Z.min(0).values) * 0.5).max()) / half_width)
+    kern = PolynomialProjectionKernel(J, 1, d, "RBF", [P[:, j:j + 1].clone() for j in range(J)], weighted=True)
+    kern.raw_lengthscales.data = inv_softplus(ls).reshape(1, -1).float()
+    sk = ScaleKernel(kern)
+    lik = GaussianLikelihood(noise_prior=SmoothedBoxPrior(1e-4, 10, sigma=0.01))
+    lik.noise = noise
+    model = ExactGPModel(X.to(dev), y.to(dev), lik, sk).to(dev)
+    model.eval()
+    return model, lik, ExactMarginalLogLikelihood(lik, model), Xs.to(dev), ys.to(dev)
+
+
 def timed(fn, reps=1):
     ts, out = [], None
     for _ in range(reps):
@@ -62,9 +89,12 @@ def predict_mode(model, lik, mll, Xs, ys, mode):
     return run
 
 
-def bench(name, N, d, J, n_test, half_width, sides, modes, out_path, reps):
+def bench(name, N, d, J, n_test, half_width, sides, modes, out_path, reps, spread=None, tag=None):
     dev = torch.device("cuda:0")
-    model, lik, mll, Xs, ys = model_of(N, d, J, n_test, half_width, dev)
+    if spread is not None:
+        model, lik, mll, Xs, ys = weighted_model_of(N, d, J, n_test, half_width, spread, dev)
+    else:
+        model, lik, mll, Xs, ys = model_of(N, d, J, n_test, half_width, dev)
     recs = []
     for on in sides:
         with settings.lowrank_posterior(on):
@@ -74,17 +104,23 @@ def bench(name, N, d, J, n_test, half_width, sides, modes, out_path, reps):
             rec = {"config": name, "N": N, "d": d, "J": J, "n_test": n_test, "half_width": half_width, "setting": on,
                    "max_rank": settings.lowrank_max_rank.value(),
                    "served": st.lowrank is not None, "strategy_build_s": round(t_build, 4)}
+            if tag:
+                rec["tag"] = tag
+            if spread is not None:
+                rec.update({"model": "rp_poly weighted k=1", "spread": spread})
             if on and st.lowrank is not None:
                 lr = st.lowrank
                 p, r, F = lr.ranks
                 rec.update({"p": p, "r": r, "F": F, "tail": lr.form.tail, "rebuilds": lr.rebuilds})
                 be = backend.get_backend()
                 f = lr.form
-                t_feat, _ = timed(lambda: be.lowrank_features(lr.Z, f.mid, f.inv_w, f.G, lr.scale, **f.kw), reps=5)
+                if spread is not None:
+                    rec["class_ranks_p_r_columns"] = lr.class_ranks
+                t_feat, _ = timed(lambda: lr._evaluate(be, lr.Z, f, lr.scale), reps=5)
                 t_gram, M = timed(lambda: lr.B.t() @ lr.B, reps=3)
                 t_fac, L = timed(lambda: torch.linalg.cholesky(lr.M), reps=3)
                 Zs = lr._test_coordinates(Xs)
-                t_tfeat, Bs = timed(lambda: be.lowrank_features(Zs, f.mid, f.inv_w, f.G, lr.scale, **f.kw), reps=3)
+                t_tfeat, Bs = timed(lambda: lr._evaluate(be, Zs, f, lr.scale), reps=3)
                 t_solve, _ = timed(lambda: lr._lower_solve(Bs.t()), reps=3)
                 rec.update({"features_ms": round(1e3 * t_feat, 3),
                             "features_write_TBps": round(8.0 * N * F / t_feat / 1e12, 3),
@@ -113,11 +149,22 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--off", action="store_true", help="also time the setting-off path")
     ap.add_argument("--max_rank", type=int, default=64, help="settings.lowrank_max_rank for every measurement (1 ... 128)")
+    ap.add_argument("--weighted", action="store_true", help="the weighted rp_poly model (k = 1) instead of additive_rp")
+    ap.add_argument("--spread", type=float, default=1.0, help="--weighted: longest / shortest lengthscale across projections")
+    ap.add_argument("--tag", default=None, help="a label copied into every record (which run, which build)")
+    ap.add_argument("--sides", default=None, help="which sides to run: on, off or on,off (default: on, and off with --off)")
     ap.add_argument("--out", default="profiles/lowrank_posterior_bench_c4.jsonl")
     a = ap.parse_args()
     settings.lowrank_max_rank._set(a.max_rank)
-    if a.config == "c4":
-        bench("C4", 50000, 20, 20, 2000, a.half_width, [True, False] if a.off else [True],
+    sides = [True, False] if a.off else [True]
+    if a.sides:
+        sides = [x == "on" for x in a.sides.split(",")]
+    if a.config == "c4" and a.weighted:
+        # mean + variances + test NLL on 2 000 rows, either side
+        bench("C4 weighted", 50000, 20, 20, 2000, a.half_width, sides, {True: ["var", "mean"], False: ["var", "mean"]}, a.out,
+              a.reps, spread=a.spread, tag=a.tag)
+    elif a.config == "c4":
+        bench("C4", 50000, 20, 20, 2000, a.half_width, sides,
               {True: ["full", "var", "mean"], False: ["full", "mean"]}, a.out, a.reps)
     else:
         # the exact N = 391 386 model (3droad's size, J = 20, no grid) with 3droad's ~43 000 test rows: mean, variances and test
