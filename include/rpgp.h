@@ -170,6 +170,26 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
                                void *stream);
 
 /*
+ * The same product and derivative with per-component weights: K = scale sum_j w_j K_j, the RBF, group-1 members of rpgp_family
+ * (below) on the plan of rpgp_lowrank_create[_tol] for the prepared buffer of the family operator's Z.  `weights`: DEVICE,
+ * J floats, of any sign (the product is linear in them); w = 1 returns the bits of the unweighted entries.  Unsharded.
+ *   rpgp_mvm_sym_lowrank_weighted: out = scale sum_{j in [j0, j1)} w_j K_j V + noise V; the weight enters the combine pass
+ *     (U_j = (float)((double)scale (double)w_j C W_j)), the other two passes are rpgp_mvm_sym_lowrank_range's.  Repeated calls
+ *     are bit-identical.  Workspace: rpgp_mvm_sym_lowrank_workspace_bytes.
+ *   rpgp_bilinear_grad_lowrank_weighted: rpgp_family_bilinear_grad's result contract (below) on the plan's Z (N x J, leading
+ *     dimension J): gZ[i][j] = scale w_j sum_i' S_ii' dk_j/dz_i for j in [j0, j1) and gcomp[j] = 0.5 sum_ii' S_ii' k_j(i, i'),
+ *     the UNWEIGHTED component sums (float64, fixed order, no atomics); columns and components outside [j0, j1) are not touched.
+ *     RPGP_EINVAL, with the outputs untouched, when the handle has no derivative rank.  Workspace:
+ *     rpgp_bilinear_grad_lowrank_workspace_bytes.
+ */
+int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const float *weights, const float *V, float *out,
+                                  int64_t N, int J, int T, int j0, int j1, float scale, float noise,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights, const float *L, const float *R, float *gZ,
+                                        float *gcomp, int64_t N, int J, int T, int j0, int j1, float scale,
+                                        void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Explicit features of the truncated kernel (the closed-form posterior of the low-rank form).  Factor C ~= G G^T (G: p x r), so
  * that every 1-D term is exp2(-h^2 (x - y)^2) ~= (G^T T(x))^T (G^T T(y)) and the kernel is K_lr = B B^T with
  * B = sqrt(scale) [T(x_1) G | ... | T(x_J) G]  (N x J r).
@@ -552,6 +572,9 @@ int rpgp_family_generic_bilinear(int dtype, int kind, int group, int ncomp, cons
                                      groups differ in size (general_rp_poly, training_routines.py:192-207) */
 #define RPGP_OP_LOWRANK 7         /* Chebyshev low-rank product (rpgp_mvm_sym_lowrank_range): prep = the plan HANDLE of
                                      rpgp_lowrank_create[_tol]; N, J, j0, j1, scale, noise as for FUSED_PREPARED; unsharded only */
+#define RPGP_OP_LOWRANK_FAMILY 8  /* the same with per-component weights (rpgp_mvm_sym_lowrank_weighted): prep = the plan HANDLE,
+                                     family = an RBF, group-1 family with ncomp == J (its device weights); any other family is
+                                     RPGP_EINVAL; N, J, j0, j1, scale, noise as for RPGP_OP_LOWRANK; unsharded only */
 typedef struct rpgp_operator {
   int kind;
   int64_t N;

@@ -54,6 +54,9 @@ SIGNATURES = {
     "rpgp_lowrank_grad_prepare": (_int, [_vp, _f64, _vp, _sz, ctypes.POINTER(ctypes.c_int), _vp]),
     "rpgp_bilinear_grad_lowrank_workspace_bytes": (_sz, [_vp, _i64, _int]),
     "rpgp_bilinear_grad_lowrank": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _f32, _vp, _sz, _vp]),
+    "rpgp_mvm_sym_lowrank_weighted": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _f32, _f32, _vp, _sz, _vp]),
+    "rpgp_bilinear_grad_lowrank_weighted": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _f32, _vp, _sz,
+                                                   _vp]),
     "rpgp_lowrank_post_select": (_int, [_f64, _f64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                          ctypes.POINTER(ctypes.c_double), _vp]),
     "rpgp_lowrank_features_f64": (_int, [_vp, _i64, _int, _int, _vp, _f64, _vp, _int, _int, _f64, _vp, _i64, _vp]),
@@ -186,6 +189,7 @@ class RpgpFamily(ctypes.Structure):
 RPGP_OP_FUSED, RPGP_OP_FUSED_PREPARED, RPGP_OP_SKI, RPGP_OP_DENSE, RPGP_OP_FAMILY, RPGP_OP_SYMCACHE = 0, 1, 2, 3, 4, 5
 RPGP_OP_SUM = 6
 RPGP_OP_LOWRANK = 7
+RPGP_OP_LOWRANK_FAMILY = 8
 RPGP_LOWRANK_GRAD_BYTES = 65536
 RPGP_KIND_RBF, RPGP_KIND_MATERN15, RPGP_KIND_IMQ, RPGP_KIND_COSINE = 0, 1, 2, 3
 RPGP_KIND_PRODUCT = 16

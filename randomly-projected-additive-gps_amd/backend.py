@@ -17,6 +17,8 @@ class HipBackend:
     mvm_sym_prepared = staticmethod(ops.mvm_sym_prepared)
     lowrank_train_plan = staticmethod(ops.lowrank_train_plan)
     bilinear_grad_lowrank = staticmethod(ops.bilinear_grad_lowrank)
+    mvm_sym_lowrank_weighted = staticmethod(ops.mvm_sym_lowrank_weighted)
+    bilinear_grad_lowrank_weighted = staticmethod(ops.bilinear_grad_lowrank_weighted)
     lowrank_post_select = staticmethod(ops.lowrank_post_select)
     lowrank_features = staticmethod(ops.lowrank_features)
     lowrank_features_grad = staticmethod(ops.lowrank_features_grad)

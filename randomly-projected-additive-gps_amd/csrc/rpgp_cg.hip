@@ -905,6 +905,15 @@ int apply_operator(const rpgp_operator *op, const ShardCtx &sh, const float *V, 
       rc = rpgp_mvm_sym_lowrank_range(op->prep, op->prep, V, out, op->N, op->J, T, op->j0, op->j1, 1, 0, op->scale, op->noise,
                                       ws, ws_bytes, stream);
       break;
+    case RPGP_OP_LOWRANK_FAMILY:
+      // (unsharded only; the weights of an RBF, group-1 family with one component per projection)
+      if (partial || world != 1) return RPGP_EINVAL;
+      if (!op->family || op->family->kind != RPGP_KIND_RBF || op->family->group != 1 || op->family->ncomp != op->J ||
+          !op->family->weights)
+        return RPGP_EINVAL;
+      rc = rpgp_mvm_sym_lowrank_weighted(op->prep, op->prep, op->family->weights, V, out, op->N, op->J, T, op->j0, op->j1,
+                                         op->scale, op->noise, ws, ws_bytes, stream);
+      break;
     case RPGP_OP_SKI:
       if (sh.mode == RPGP_SHARD_ROWS) {
         const size_t nh = (size_t)op->J * op->G * T;
@@ -960,6 +969,7 @@ size_t operator_workspace(const rpgp_operator *op, int T) {
     case RPGP_OP_FUSED_PREPARED:
       return rpgp_mvm_sym_range_workspace_bytes(op->N, T, world, rank);
     case RPGP_OP_LOWRANK:
+    case RPGP_OP_LOWRANK_FAMILY:
       return rpgp_mvm_sym_lowrank_workspace_bytes(op->prep, op->N, T);
     case RPGP_OP_SKI:
       return rpgp_ski_workspace_bytes(op->J, op->G, T);

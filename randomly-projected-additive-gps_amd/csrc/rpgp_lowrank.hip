@@ -427,6 +427,93 @@ int launch_lowrank(const LowrankPlan &P, const float *V, float *out, int N, int 
   return (int)hipGetLastError();
 }
 
+// ---- per-component weights (rpgp_mvm_sym_lowrank_weighted: the RBF, group-1 members of rpgp_family) ---------------------------
+// K = scale sum_j w_j K_j is linear in the weights and every K_j shares the plan's one form, so w_j enters the product in
+// exactly one place: pass (b) of projection j.  The kernels below are lr_combine_kernel, lrg_combine_kernel and
+// lrg_output_kernel with that factor (and, for the derivative, one sum per component in place of the single gscale); they are
+// kernels of their own, not a template argument of the unweighted ones, so that those keep their names and their code.
+//
+// (b) U[jj][t][m] = (scale w[j0 + jj]) * sum_n c_mn W[n]: lr_combine_kernel's loads, block-partial order, chunking and single
+// round trip, with the weight requested beside the partials and the factor scale * w formed in float64 (w = 1: the same bits).
+// `w` points at the weight of projection j0.
+template <int PB>
+__global__ __launch_bounds__(256) void lrw_combine_kernel(const double *__restrict__ part, const float *__restrict__ coef,
+                                                          const float *__restrict__ w, float *__restrict__ U, int nblk, int T,
+                                                          int jn, float scale) {
+  constexpr int G = 256 / PB;
+  constexpr int CH = ((PB + G - 1) / G + 3) & ~3, NCH = (PB + CH - 1) / CH;
+  static_assert(NCH <= G, "a chunk of the coefficient row per group");
+  __shared__ double sw[G][PB];
+  __shared__ double ws[PB];
+  const int jj = blockIdx.x, t = blockIdx.y;
+  const int n = threadIdx.x % PB, g = threadIdx.x / PB;
+  const size_t bstride = (size_t)jn * T * PB;
+  const double *p = part + ((size_t)jj * T + t) * PB + n;
+  double pv[kCombineBatch];
+#pragma unroll
+  for (int k = 0; k < kCombineBatch; ++k) {
+    const int b = g + k * G;
+    pv[k] = p[(size_t)(b < nblk ? b : nblk - 1) * bstride];
+  }
+  float4v c[CH / 4];
+#pragma unroll
+  for (int k = 0; k < CH / 4; ++k) {
+    const int col = g * CH + 4 * k;
+    c[k] = *reinterpret_cast<const float4v *>(coef + n * PB + (col < PB ? col : PB - 4));
+  }
+  const float wj = w[jj];
+  __builtin_amdgcn_sched_barrier(0);                      // (every load above is in flight before the first add)
+  double s = 0.0;
+#pragma unroll
+  for (int k = 0; k < kCombineBatch; ++k) s += g + k * G < nblk ? pv[k] : 0.0;
+  for (int b0 = g + kCombineBatch * G; b0 < nblk; b0 += kCombineBatch * G) {
+#pragma unroll
+    for (int k = 0; k < kCombineBatch; ++k) {
+      const int b = b0 + k * G;
+      pv[k] = p[(size_t)(b < nblk ? b : nblk - 1) * bstride];
+    }
+#pragma unroll
+    for (int k = 0; k < kCombineBatch; ++k) s += b0 + k * G < nblk ? pv[k] : 0.0;
+  }
+  if (g < G) sw[g][n] = s;
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    double a = sw[0][threadIdx.x];
+#pragma unroll
+    for (int q = 1; q < G; ++q) a += sw[q][threadIdx.x];
+    ws[threadIdx.x] = a;
+  }
+  __syncthreads();
+  if (g < NCH) {                                          // (sw is free again: its readers are past the barrier)
+    double a = 0.0;
+#pragma unroll
+    for (int k = 0; k < CH; ++k) {
+      const int col = g * CH + k;
+      if (col < PB) a = __builtin_fma((double)c[k >> 2][k & 3], ws[col], a);
+    }
+    sw[g][n] = a;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    const int m = threadIdx.x;
+    double a = sw[0][m];
+#pragma unroll
+    for (int q = 1; q < NCH; ++q) a += sw[q][m];
+    U[((size_t)jj * T + t) * PB + m] = (float)(((double)scale * (double)wj) * a);
+  }
+}
+
+template <int PB>
+int launch_lowrank_weighted(const LowrankPlan &P, const float *w, const float *V, float *out, int N, int T, int j0, int jn,
+                            float scale, float noise, double *part, float *U, hipStream_t st) {
+  const int nblk = proj_blocks(N);
+  hipLaunchKernelGGL(lr_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, V, part, N, T, j0, jn);
+  hipLaunchKernelGGL(lrw_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, w + j0, U, nblk, T, jn, scale);
+  hipLaunchKernelGGL(lr_output_kernel<PB>, dim3((N + kOutRows - 1) / kOutRows, T), dim3(256), 0, st, P.xt, U, V, out, N, T,
+                     j0, jn, 0, N, noise);
+  return (int)hipGetLastError();
+}
+
 
 // ---- bilinear derivative ----------------------------------------------------------------------------------------
 // (a) lr_project_kernel with the Chebyshev recurrence in float64: near |x| = 1 the fp32 recurrence's error grows with m, which
@@ -609,6 +696,136 @@ int launch_grad(const LowrankPlan &P, const float *L, const float *R, float *gZ,
                      jn, P.p, P.pb, (double)scale);
   hipLaunchKernelGGL(lrg_output_kernel<QB>, dim3((N + kOutRows - 1) / kOutRows), dim3(256), 0, st, P.xt, U, gsp, L, R, gZ,
                      gscale, N, T, j0, jn, ldg);
+  return (int)hipGetLastError();
+}
+
+// The weighted derivative (rpgp_bilinear_grad_lowrank_weighted).  (b) is lrg_combine_kernel with U^R, U^L carrying
+// scale * w[j0 + jj] (float64; w = 1: the same bits) and gsp left as it is, the UNWEIGHTED W^L^T C W^R of the component.
+// `w` points at the weight of projection j0.
+template <int PB, int QB>
+__global__ __launch_bounds__(256) void lrgw_combine_kernel(const double *__restrict__ partL, const double *__restrict__ partR,
+                                                           const double *__restrict__ dcoef, const double *__restrict__ ccoef,
+                                                           const float *__restrict__ wt, double *__restrict__ U,
+                                                           double *__restrict__ gsp, int nblk, int T, int jn, int p, int pc,
+                                                           double scale) {
+  constexpr int G = 256 / PB;
+  __shared__ double sw[2][G][PB];
+  __shared__ double w[2][PB];
+  __shared__ double cw[PB];
+  const int jj = blockIdx.x, t = blockIdx.y;
+  const int n = threadIdx.x % PB, g = threadIdx.x / PB;
+  const double sj = scale * (double)wt[jj];
+  if (g < G) {
+    double sl = 0.0, sr = 0.0;
+    for (int b = g; b < nblk; b += G) {
+      const size_t o = (((size_t)b * jn + jj) * T + t) * PB + n;
+      sl += partL[o];
+      sr += partR[o];
+    }
+    sw[0][g][n] = sl;
+    sw[1][g][n] = sr;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    double sl = sw[0][0][threadIdx.x], sr = sw[1][0][threadIdx.x];
+#pragma unroll
+    for (int k = 1; k < G; ++k) {
+      sl += sw[0][k][threadIdx.x];
+      sr += sw[1][k][threadIdx.x];
+    }
+    w[0][threadIdx.x] = sl;
+    w[1][threadIdx.x] = sr;
+  }
+  __syncthreads();
+  const int m = threadIdx.x;
+  if (m < QB) {
+    double ur = 0.0, ul = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < QB; ++k) {
+      const double d = dcoef[m * QB + k];
+      ur = __builtin_fma(d, w[1][k], ur);
+      ul = __builtin_fma(d, w[0][k], ul);
+    }
+    double *u = U + ((size_t)jj * T + t) * 2 * QB;
+    u[m] = sj * ur;
+    u[QB + m] = sj * ul;
+  }
+  if (m < PB) {                                           // (C W^R)[m], zero beyond p
+    double s = 0.0;
+    if (m < p)
+      for (int k = 0; k < p; ++k) s = __builtin_fma(ccoef[m * pc + k], w[1][k], s);
+    cw[m] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < p; ++k) s = __builtin_fma(w[0][k], cw[k], s);
+    gsp[(size_t)jj * T + t] = s;
+  }
+}
+
+// (c) is lrg_output_kernel with one sum per component in place of the single gscale: thread jj < jn of workgroup 0 writes
+// gcomp[j0 + jj] = sum_t gsp[jj][t] (float64, t ascending; jn <= 64 < 256 threads), rpgp_family_bilinear_grad's unweighted sums.
+// gZ has the leading dimension J of the plan.  grid (row blocks of 64)
+template <int QB>
+__global__ __launch_bounds__(256) void lrgw_output_kernel(const float *__restrict__ xt, const double *__restrict__ U,
+                                                          const double *__restrict__ gsp, const float *__restrict__ L,
+                                                          const float *__restrict__ R, float *__restrict__ gZ,
+                                                          float *__restrict__ gcomp, int N, int T, int j0, int jn, int ldg) {
+  __shared__ float sres[kOutRows][kPrepMaxJ + 1];
+  const int r = threadIdx.x & (kOutRows - 1);
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
+  const int row0 = blockIdx.x * kOutRows;
+  const int i = row0 + r;
+  const bool ok = i < N;
+  for (int jj = wv; jj < jn; jj += 4) {
+    const double *u = U + (size_t)jj * T * 2 * QB;
+    double q[QB];
+#pragma unroll
+    for (int m = 0; m < QB; ++m) q[m] = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const double l = ok ? (double)L[(size_t)i * T + t] : 0.0;
+      const double rr = ok ? (double)R[(size_t)i * T + t] : 0.0;
+      const double *ut = u + (size_t)t * 2 * QB;
+#pragma unroll
+      for (int m = 0; m < QB; ++m) q[m] = __builtin_fma(l, ut[m], __builtin_fma(rr, ut[QB + m], q[m]));
+    }
+    const double x = ok ? (double)xt[(size_t)(j0 + jj) * N + i] : 0.0, x2 = 2.0 * x;
+    double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = QB - 1; k >= 1; --k) {
+      const double bk = __builtin_fma(x2, b1, q[k] - b2);
+      b2 = b1;
+      b1 = bk;
+    }
+    sres[r][jj] = (float)__builtin_fma(x, b1, q[0] - b2);
+  }
+  __syncthreads();
+  const int rows = N - row0 < kOutRows ? N - row0 : kOutRows;
+  for (int e = threadIdx.x; e < rows * jn; e += 256) {
+    const int rr = e / jn, c = e - rr * jn;
+    gZ[(size_t)(row0 + rr) * ldg + j0 + c] = sres[rr][c];
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < jn) {
+    double s = 0.0;
+    for (int t = 0; t < T; ++t) s += gsp[(size_t)threadIdx.x * T + t];
+    gcomp[j0 + threadIdx.x] = (float)s;
+  }
+}
+
+template <int PB, int QB>
+int launch_grad_weighted(const LowrankPlan &P, const float *w, const float *L, const float *R, float *gZ, float *gcomp, int N,
+                         int T, int j0, int jn, float scale, void *ws, hipStream_t st) {
+  const int nblk = proj_blocks(N);
+  const size_t np = (size_t)nblk * jn * T * PB;
+  double *partL = reinterpret_cast<double *>(ws), *partR = partL + np;
+  double *U = partR + np, *gsp = U + (size_t)jn * T * 2 * QB;
+  hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, L, partL, N, T, j0, jn);
+  hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, R, partR, N, T, j0, jn);
+  hipLaunchKernelGGL((lrgw_combine_kernel<PB, QB>), dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, w + j0, U, gsp,
+                     nblk, T, jn, P.p, P.pb, (double)scale);
+  hipLaunchKernelGGL(lrgw_output_kernel<QB>, dim3((N + kOutRows - 1) / kOutRows), dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gcomp,
+                     N, T, j0, jn, P.J);
   return (int)hipGetLastError();
 }
 
@@ -1242,6 +1459,51 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
       constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;
       if constexpr (PB >= QB)
         return launch_grad<PB, QB>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st);
+      else
+        return RPGP_EINVAL;
+    });
+  });
+}
+
+int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const float *weights, const float *V, float *out,
+                                  int64_t N, int J, int T, int j0, int j1, float scale, float noise, void *workspace,
+                                  size_t workspace_bytes, void *stream) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P || !prep || !weights || !V || !out || N <= 0 || T <= 0 || J <= 0 || J > kPrepMaxJ || j0 < 0 || j1 <= j0 || j1 > J)
+    return RPGP_EINVAL;
+  if (N != P->N || J != P->J || T > 65535) return RPGP_EINVAL;
+  const size_t need = rpgp_mvm_sym_lowrank_workspace_bytes(handle, N, T);
+  if (!workspace || workspace_bytes < need) return RPGP_EWORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int n = (int)N, jn = j1 - j0;
+  double *part = reinterpret_cast<double *>(workspace);
+  float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
+  const bool prof = rpgp_internal::prof_open(st);
+  int rc = dispatch_pb<kMaxRank>(P->pb, [&](auto pb) {
+    return launch_lowrank_weighted<decltype(pb)::value>(*P, weights, V, out, n, T, j0, jn, scale, noise, part, U, st);
+  });
+  if (prof) {
+    const int pc = rpgp_internal::prof_close(st);
+    if (!rc) rc = pc;
+  }
+  return rc;
+}
+
+int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights, const float *L, const float *R, float *gZ,
+                                        float *gcomp, int64_t N, int J, int T, int j0, int j1, float scale, void *workspace,
+                                        size_t workspace_bytes, void *stream) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P || !weights || !L || !R || !gZ || !gcomp || N <= 0 || T <= 0 || T > 65535) return RPGP_EINVAL;
+  if (N != P->N || J != P->J || j0 < 0 || j1 <= j0 || j1 > J) return RPGP_EINVAL;
+  if (!P->q) return RPGP_EINVAL;                          // no derivative rank: the caller runs rpgp_family_bilinear_grad
+  if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int n = (int)N, jn = j1 - j0;
+  return dispatch_pb<kMaxRank>(P->qb, [&](auto qb) {
+    return dispatch_pb<kMaxRank>(grad_pb(*P), [&](auto pb) -> int {
+      constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;
+      if constexpr (PB >= QB)
+        return launch_grad_weighted<PB, QB>(*P, weights, L, R, gZ, gcomp, n, T, j0, jn, scale, workspace, st);
       else
         return RPGP_EINVAL;
     });

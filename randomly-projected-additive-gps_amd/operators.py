@@ -828,10 +828,40 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         self._generic = bool(getattr(self.fam, "generic", False))
         self._wsum = float(w.sum())                 # one host sync per construction (= per optimiser step)
 
+    def lowrank_form(self, noise=None):
+        """The plain operator's protocol for the weighted kinds: the training plan of the ONE Chebyshev form shared by every
+        column of Z (the lengthscales are folded into the columns; a component weight is a factor of the combine pass) that
+        serves this operator's solves and derivative under settings.lowrank_kernel, or None for the family sweep.  Served: a
+        symmetric float32 RBF operator with k = 1 and J <= 64, a backend with the weighted entries, a known positive noise and
+        a plan with p, q <= 64 at the tolerance of the kernel's diagonal mass scale * sum_c |w_c| (weights of any sign: the
+        product is linear in them).  Decided ONCE per operator, like the plain operator's."""
+        if getattr(self, "_lowrank", None) is None:
+            self._lowrank = False
+            be = _backend.get_backend()
+            plan_fn, prepare = getattr(be, "lowrank_train_plan", None), getattr(be, "prepare", None)
+            if noise is None:
+                noise = getattr(self, "_noise_host", None)
+            if settings.lowrank_kernel.on() and type(self) is FamilyAdditiveOperator and self.symmetric and \
+                    self.Z1.dtype == torch.float32 and self.kind == "RBF" and self.group == 1 and not self.product and \
+                    not self._generic and self.num_projections <= 64 and plan_fn is not None and prepare is not None and \
+                    hasattr(be, "mvm_sym_lowrank_weighted") and hasattr(be, "bilinear_grad_lowrank_weighted") and \
+                    noise is not None and float(noise) > 0.0:
+                if self._prep is None:
+                    self._prep = prepare(self.Z1.detach())
+                if self._prep.fast_ok:
+                    wabs = float(self.fam.weights.abs().sum())
+                    plan = plan_fn(self._prep, self._scale, float(noise), mass=self._scale * wabs)
+                    if plan is not None:
+                        self._lowrank = plan
+        return self._lowrank or None
+
     def _local_matmul(self, rhs, noise=0.0):
         be = _backend.get_backend()
         z1 = self.Z1.detach()
         if self.symmetric:
+            lr = getattr(self, "_lowrank", None)       # (only a plan decided under settings.lowrank_kernel: lowrank_form)
+            if lr:
+                return be.mvm_sym_lowrank_weighted(lr, self._prep, self.fam.weights, rhs, self._scale, noise)
             return be.family_mvm_sym(self.fam, z1, rhs, self._scale, noise)
         return be.family_mvm_rect(self.fam, z1, self.Z2.detach(), rhs, self._scale)
 
@@ -853,6 +883,10 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         if not self.symmetric or not hasattr(be, "mbcg_solve") or self._generic:
             return None
         from . import _lib
+        lr = self.lowrank_form(noise) if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        if lr is not None:
+            return be.make_operator_desc(_lib.RPGP_OP_LOWRANK_FAMILY, self.Z1.shape[0], self.Z1.shape[1], self._scale, noise,
+                                         family=self.fam, lowrank=lr)
         z1 = self.Z1.detach().contiguous()
         return be.make_operator_desc(_lib.RPGP_OP_FAMILY, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1,
                                      family=self.fam)
@@ -895,8 +929,13 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
     def _bilinear_derivative(self, left_vecs, right_vecs):
         if not self.symmetric:
             raise NotImplementedError("derivatives are only needed for the train-train kernel")
-        gZ, gc = _backend.get_backend().family_bilinear_grad(self.fam, self.Z1.detach(), left_vecs.detach(),
-                                                            right_vecs.detach(), self._scale)
+        be = _backend.get_backend()
+        lr = self.lowrank_form() if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        if lr is not None:
+            gZ, gc = be.bilinear_grad_lowrank_weighted(lr, self.fam.weights, left_vecs.detach(), right_vecs.detach(),
+                                                       self._scale)
+        else:
+            gZ, gc = be.family_bilinear_grad(self.fam, self.Z1.detach(), left_vecs.detach(), right_vecs.detach(), self._scale)
         return self._finish_grads(gZ, gc)
 
     _quad_form_derivative = _bilinear_derivative

@@ -314,12 +314,14 @@ class LowrankTrainPlan:
             self.handle = None
 
 
-def lowrank_train_plan(prep, scale, noise):
+def lowrank_train_plan(prep, scale, noise, mass=None):
     """The training plan of `prep` for this step's (N, scale, noise), or None when the low-rank form does not serve it (switch
-    off, not fast_ok, no tolerance, or p or q above 64).  Built once per Prepared and tolerance."""
+    off, not fast_ok, no tolerance, or p or q above 64).  Built once per Prepared and tolerance.  `mass`: the kernel's diagonal
+    mass when it is not scale * J — scale * sum_c |w_c| of a weighted family operator, so that lowrank_train_tol's spectral
+    bound holds for it."""
     if not lowrank_enabled() or not prep.fast_ok:
         return None
-    tol = lowrank_train_tol(prep.N, prep.J, scale, noise)
+    tol = lowrank_train_tol(prep.N, prep.J, scale, noise) if mass is None else lowrank_train_tol(prep.N, 1, mass, noise)
     if not tol:
         return None
     cached = getattr(prep, "_train", None)
@@ -548,6 +550,61 @@ def bilinear_grad_lowrank(plan, L, R, scale, j0=0, j1=None):
                                                   J, T, j0, j1, float(scale), ws.data_ptr(), ws.numel(), _stream()),
                    "rpgp_bilinear_grad_lowrank")
     return gZ, gs
+
+
+def _lowrank_weights(plan, weights, what):
+    """The per-component weights of the weighted low-rank entries: J float32 values on the plan's device (ValueError otherwise,
+    before any launch)."""
+    if not torch.is_tensor(weights) or weights.dtype != torch.float32 or weights.device != plan.device or \
+            weights.numel() != plan.J:
+        raise ValueError("%s: weights must be %d float32 values on %s" % (what, plan.J, plan.device))
+    return weights.detach().reshape(-1).contiguous()
+
+
+def mvm_sym_lowrank_weighted(plan, prep, weights, V, scale, noise=0.0, j0=0, j1=None, out=None):
+    """out = scale * sum_{j in [j0, j1)} w_j K_j V + noise * V on the Z that `prep` and its LowrankTrainPlan `plan` were built
+    from (rpgp_mvm_sym_lowrank_weighted): the RBF, group-1 family operator through the low-rank form.  Unsharded."""
+    lib = _lib.load()
+    w = _lowrank_weights(plan, weights, "mvm_sym_lowrank_weighted")
+    N, J = plan.N, plan.J
+    j1 = J if j1 is None else j1
+    V2, squeeze = _as_matrix(V, N, "V")
+    T = V2.shape[1]
+    if out is None:
+        out = torch.empty_like(V2)
+    with _on(plan.device):
+        nbytes = lib.rpgp_mvm_sym_lowrank_workspace_bytes(plan.handle, N, T)
+        ws = _workspace(plan.device, nbytes)
+        _lib.check(lib.rpgp_mvm_sym_lowrank_weighted(plan.handle, prep.buf.data_ptr(), w.data_ptr(), V2.data_ptr(),
+                                                     out.data_ptr(), N, J, T, j0, j1, float(scale), float(noise),
+                                                     ws.data_ptr(), ws.numel(), _stream()), "rpgp_mvm_sym_lowrank_weighted")
+    return out.squeeze(1) if squeeze else out
+
+
+def bilinear_grad_lowrank_weighted(plan, weights, L, R, scale, j0=0, j1=None):
+    """(gZ [N x J], gcomp [J]) of family_bilinear_grad for the RBF, group-1 family on the plan's Z, from the low-rank form
+    (rpgp_bilinear_grad_lowrank_weighted): gZ carries scale * w_j, gcomp are the unweighted per-component sums.  The columns and
+    components outside [j0, j1) are zero."""
+    lib = _lib.load()
+    w = _lowrank_weights(plan, weights, "bilinear_grad_lowrank_weighted")
+    N, J = plan.N, plan.J
+    j1 = J if j1 is None else j1
+    L2, _ = _as_matrix(L, N, "L")
+    R2, _ = _as_matrix(R, N, "R")
+    if L2.shape != R2.shape:
+        raise ValueError("L and R must have the same shape")
+    T = L2.shape[1]
+    alloc = torch.empty if (j0 == 0 and j1 == J) else torch.zeros
+    gZ = alloc((N, J), dtype=torch.float32, device=plan.device)
+    gc = alloc((J,), dtype=torch.float32, device=plan.device)
+    with _on(plan.device):
+        nbytes = lib.rpgp_bilinear_grad_lowrank_workspace_bytes(plan.handle, N, T)
+        ws = _workspace(plan.device, nbytes)
+        _lib.check(lib.rpgp_bilinear_grad_lowrank_weighted(plan.handle, w.data_ptr(), L2.data_ptr(), R2.data_ptr(),
+                                                           gZ.data_ptr(), gc.data_ptr(), N, J, T, j0, j1, float(scale),
+                                                           ws.data_ptr(), ws.numel(), _stream()),
+                   "rpgp_bilinear_grad_lowrank_weighted")
+    return gZ, gc
 
 
 def mvm_sym_prepared(prep, V, scale, noise=0.0, j0=0, j1=None, out=None, shard=None):

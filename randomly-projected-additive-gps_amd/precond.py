@@ -302,6 +302,11 @@ def start_factorisation_warmup(n, device):
     _warm_started.add(key)
     finish_factorisation_warmup()
     import threading
+    if len(_warm_started) == 1:
+        # a process that ends while the helper thread is still inside the libraries' first-use loads (a fit of a few fast
+        # steps: 20 low-rank steps at N = 50 000 take 0.3 s) aborts at interpreter teardown: join it before that
+        import atexit
+        atexit.register(finish_factorisation_warmup)
     side = torch.cuda.Stream(device=dev)
 
     def work():

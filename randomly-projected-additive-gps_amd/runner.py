@@ -247,7 +247,8 @@ def build_parser():
     p.add_argument("--no_cache_kernel", dest="cache_kernel", action="store_const", const=False,
                    help="(rpgp) never materialise K: every CG iteration runs the fused recompute-in-kernel MVM")
     p.add_argument("--lowrank_kernel", action="store_true",
-                   help="(rpgp) train and solve the exact kernel through its Chebyshev low-rank form where its ranks fit")
+                   help="(rpgp) train and solve the exact kernel through its Chebyshev low-rank form where its ranks fit: "
+                        "additive_rp and the weighted rp_poly / strictly_additive kinds with k = 1 and RBF sub-kernels")
     p.add_argument("--lowrank_posterior", action="store_true",
                    help="(rpgp) predict in closed form from the explicit features of the Chebyshev low-rank kernel where served")
     p.add_argument("--lowrank_mll", action="store_true",

@@ -136,6 +136,10 @@ native_sharded_cg = _setting("native_sharded_cg", True, flag=True)
 # additive-RP operator whose plan at the training tolerance (per-entry tail <= min(2^-26, 1e-3 noise / (scale J N))) has ranks
 # p, q <= 64 is solved through RPGP_OP_LOWRANK (no packed / dense cache) and differentiated by rpgp_bilinear_grad_lowrank — both
 # or neither, decided once per operator.  Off: the exact sweep.  RPGP_LOWRANK=0 and RPGP_FACT_ASM keep the sweep either way.
+# The weighted kinds (FamilyAdditiveOperator: RBF, k = 1, one lengthscale and one weight of any sign per projection, J <= 64) are
+# served the same way on the one form shared by every column, at the tolerance of the kernel's diagonal mass
+# (1e-3 noise / (scale sum_c |w_c| N)): the solve through RPGP_OP_LOWRANK_FAMILY, the derivative by
+# rpgp_bilinear_grad_lowrank_weighted.  Mixed group sizes, SKI, k > 1 and the other sub-kernels keep the family sweep.
 lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
 # prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
 # with a float64 twin (k = 1, no grid), J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default, up to 128), at most 4096
