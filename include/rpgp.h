@@ -152,7 +152,8 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
  *     the smallest q whose discarded tail sum_{max(m,n) >= q} |d_mn| is <= min(tol, 2^-26); 0 above q_max (<= 128).
  *     `coef_host` (optional, q_max x q_max row-major) receives D.
  *   rpgp_lowrank_grad_prepare: chooses q for the plan's h and stores D and the plan's own coefficients C (both float64) in the
- *     caller's device buffer of RPGP_LOWRANK_GRAD_BYTES, which must outlive the handle's derivative calls.  *q_host = 0 (no derivative rank) when q > 64
+ *     caller's device buffer of RPGP_LOWRANK_GRAD_BYTES (rpgp_lowrank_grad_bytes(handle) for a plan of rpgp_lowrank_create_cap,
+ *     below), which must outlive the handle's derivative calls.  *q_host = 0 (no derivative rank) when q > 64 (the plan's cap)
  *     or the plan has rank 1.  Synchronises the stream.  A later call replaces the rank.
  *   rpgp_bilinear_grad_lowrank: rpgp_bilinear_grad's result contract (gZ for the columns [j0, j1) only — the others are not
  *     touched —, gscale) on the plan's Z, any T, computed from the product form in four launches with float64 reductions in a
@@ -188,6 +189,31 @@ int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const fl
 int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights, const float *L, const float *R, float *gZ,
                                         float *gcomp, int64_t N, int J, int T, int j0, int j1, float scale,
                                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Plans with a rank cap of the caller's, up to 128 (half-widths up to about 14, where the reference degree 128 stops resolving
+ * the function).  The creators above size their buffers for rank 64 and keep doing so; a plan made here remembers its cap, and
+ * every entry that takes a handle — rpgp_mvm_sym_lowrank_range, rpgp_mvm_sym_lowrank_weighted, rpgp_lowrank_grad_prepare,
+ * rpgp_bilinear_grad_lowrank[_weighted], the two *_workspace_bytes, rpgp_mbcg_workspace_bytes and the executor's
+ * RPGP_OP_LOWRANK / RPGP_OP_LOWRANK_FAMILY — serves its padded ranks 8 ... 128 with the contracts stated above.  Padded ranks
+ * above 64 run kernels of their own (the projection in two rank slices per row block, float64 Clenshaw sums in both output
+ * passes); a plan whose p and q are <= 64 runs the kernels, and returns the bits, of a plan of rpgp_lowrank_create_tol.
+ *   rpgp_lowrank_plan_bytes_cap: size of the plan buffer for the cap p_max (1 ... 128; 0 outside, or for N, J outside
+ *     rpgp_lowrank_plan_bytes' limits).  p_max <= 64: rpgp_lowrank_plan_bytes(N, J).
+ *   rpgp_lowrank_create_cap: rpgp_lowrank_create_tol with the cap p_max: *p_host = 0 and *handle_host = NULL when the range
+ *     needs more than p_max.  RPGP_EINVAL for p_max outside 1 ... 128.  Like the other creators it does not read the prepared
+ *     header's fast_ok (that guards the factorised sweep's exp2 range; this form reads the centred coordinates only) and
+ *     serves any finite max_abs the reference degree resolves; a non-finite max_abs is not served.  The coordinates themselves
+ *     are the caller's to vouch for: rpgp_prepare's max_abs skips a NaN of Z (its fast_ok is then 0), so a caller that serves
+ *     buffers that are not fast_ok checks the prepared coordinates for NaN first, as ops.LowrankTrainPlan does.
+ *   rpgp_lowrank_grad_bytes: size of rpgp_lowrank_grad_prepare's buffer for this handle: RPGP_LOWRANK_GRAD_BYTES for a plan of
+ *     rpgp_lowrank_create[_tol] or a cap <= 64, D and C (float64) at the padded cap above; 0 for a NULL handle.
+ *     rpgp_lowrank_grad_prepare requires that many bytes and selects q up to the plan's cap.
+ */
+size_t rpgp_lowrank_plan_bytes_cap(int64_t N, int J, int p_max);
+int rpgp_lowrank_create_cap(const void *prep, int64_t N, int J, float max_abs, double tol, int p_max, void *plan,
+                            size_t plan_bytes, int *p_host, void **handle_host, void *stream);
+size_t rpgp_lowrank_grad_bytes(const void *handle);
 
 /*
  * Explicit features of the truncated kernel (the closed-form posterior of the low-rank form).  Factor C ~= G G^T (G: p x r), so

@@ -50,6 +50,10 @@ SIGNATURES = {
                                           _vp]),
     "rpgp_lowrank_create_tol": (_int, [_vp, _i64, _int, _f32, _f64, _vp, _sz, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(_vp), _vp]),
+    "rpgp_lowrank_plan_bytes_cap": (_sz, [_i64, _int, _int]),
+    "rpgp_lowrank_create_cap": (_int, [_vp, _i64, _int, _f32, _f64, _int, _vp, _sz, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(_vp), _vp]),
+    "rpgp_lowrank_grad_bytes": (_sz, [_vp]),
     "rpgp_lowrank_grad_select": (_int, [_f64, _int, _f64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), _vp]),
     "rpgp_lowrank_grad_prepare": (_int, [_vp, _f64, _vp, _sz, ctypes.POINTER(ctypes.c_int), _vp]),
     "rpgp_bilinear_grad_lowrank_workspace_bytes": (_sz, [_vp, _i64, _int]),

@@ -32,6 +32,12 @@
 // one body (lr_features_body) with an epilogue each, for every padded rank 8 ... 128: G in static LDS up to 64, in dynamic LDS
 // above.
 //
+// Ranks above 64 (plans of rpgp_lowrank_create_cap, up to 128): the kernels above keep one float64 value per rank and lane, which
+// stops fitting the register file at 64, so padded ranks 72 ... 128 run forms of their own — the projection in two rank slices
+// per row block (lrx_project_kernel), the product's output pass with a float64 Clenshaw sum (lrx_output_kernel), the
+// derivative's with its sum split at 64 (lrgx_output_kernel) and its combine with the ranks as arguments (lrgx_combine_kernel).
+// DESIGN.md 7.8.
+//
 // Every kernel is templated on the padded rank; dispatch_pb turns the runtime value into the template argument.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -54,7 +60,8 @@ constexpr int kPrepRowdatOffsetFloats = 128;
 constexpr int kPrepMaxJ = 64;
 
 constexpr int kRefDegree = 128;          // reference degree of the 2-D Chebyshev interpolant (rank selection)
-constexpr int kMaxRank = 64;             // largest rank a plan serves (PB <= 64 floats of accumulators per lane)
+constexpr int kMaxRank = 64;             // largest rank of a plan of rpgp_lowrank_create[_tol] (PB <= 64 accumulators per lane)
+constexpr int kCapRank = 128;            // largest rank of a plan of rpgp_lowrank_create_cap (the lrx / lrgx kernels above 64)
 constexpr double kTailTol = 1.0 / (1 << 26);
 constexpr double kKappa = 0.84932180028801907;   // (2 ln 2)^-1/2
 constexpr int kProjRowsPerThread = 8;    // pass (a): 2 048 rows per workgroup
@@ -73,7 +80,12 @@ struct LowrankPlan {
   const double *dcoef = nullptr;         // qb x qb, fp64 (in z units), zero outside q x q
   const double *ccoef = nullptr;         // pb x pb, fp64: the coefficients whose fp32 rounding is `coef` (gscale)
   double tol = 0.0;                      // the plan's tail tolerance
+  int cap = kMaxRank;                    // largest rank the plan selects (rpgp_lowrank_create_cap: up to kCapRank)
+  int ld = kMaxRank;                     // its buffers hold ld x ld coefficients: 64, or the padded cap above 64
 };
+
+// side of the coefficient blocks of a plan with the rank cap `cap`: rpgp_lowrank_create's 64 up to there, the padded cap above
+inline int cap_ld(int cap) { return cap <= kMaxRank ? kMaxRank : (cap + 7) & ~7; }
 
 inline int pad8(int p) { return (p + 7) & ~7; }
 inline int proj_blocks(int64_t N) { return (int)((N + kProjRows - 1) / kProjRows); }
@@ -829,6 +841,333 @@ int launch_grad_weighted(const LowrankPlan &P, const float *w, const float *L, c
   return (int)hipGetLastError();
 }
 
+// ---- padded ranks 72 ... 128 of the product and the derivative (plans of rpgp_lowrank_create_cap) ---------------------------
+// The kernels above keep PB (or QB) float64 values per lane, two VGPRs each: 155 VGPRs at 64, more than the register file at
+// 128.  The kernels below are their forms for 64 < PB <= 128, kernels of their own so that every kernel above keeps its code.
+//
+// (a) One kernel for the product and the derivative.  A workgroup owns a rank slice of a row block: slice 0 the ranks
+// [0, 64), slice 1 the ranks [64, PB) (8 ... 64 of them).  It runs the float64 recurrence up to its slice's upper end — one
+// v_fma_f64 per rank below the slice — and accumulates its own slice only, so a lane holds at most 64 accumulators, and then
+// reduces them with lr_project_kernel's transposed exchange at the slice's offset.  The order of every addition is a function
+// of PB alone; part[b][jj][t][PB] as above.  The slice is the low bit of blockIdx.x (the z dimension is T, up to 65 535).
+template <int LO, int CNT, int PB>
+__device__ __forceinline__ void lrx_project_slice(const float (&xv)[kProjRowsPerThread], const float (&vv)[kProjRowsPerThread],
+                                                  int r0, int N, double *__restrict__ red, double *__restrict__ dst) {
+  static_assert(CNT >= 8 && CNT <= 64 && CNT % 8 == 0 && LO + CNT == (LO ? PB : 64), "a slice of at most 64 ranks");
+  double acc[CNT];
+#pragma unroll
+  for (int m = 0; m < CNT; ++m) acc[m] = 0.0;
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {
+    const double xi = (double)xv[u], v = r0 + u * 256 < N ? (double)vv[u] : 0.0, x2 = 2.0 * xi;
+    double tm2 = 1.0, tm1 = xi;
+    if constexpr (LO == 0) {
+      acc[0] += v;
+      acc[1] = __builtin_fma(xi, v, acc[1]);
+    }
+#pragma unroll
+    for (int m = 2; m < LO + CNT; ++m) {
+      const double tm = __builtin_fma(x2, tm1, -tm2);     // T_m = 2x T_{m-1} - T_{m-2}
+      if (m >= LO) acc[m - LO] = __builtin_fma(tm, v, acc[m - LO]);
+      tm2 = tm1;
+      tm1 = tm;
+    }
+  }
+  constexpr int QB = CNT / 4;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < CNT / 2; ++i) acc[i] = swap_add<32>(acc[i], acc[i + CNT / 2]);
+#pragma unroll
+  for (int i = 0; i < QB; ++i) {
+    double s = swap_add<16>(acc[i], acc[i + QB]);
+    s += dpp_d<0xb1>(s);    // quad_perm [1,0,3,2]
+    s += dpp_d<0x4e>(s);    // quad_perm [2,3,0,1]
+    s += dpp_d<0x141>(s);   // row_half_mirror
+    s += dpp_d<0x140>(s);   // row_mirror
+    if ((lane & 15) == i) red[w * CNT + QB * (lane >> 4) + i] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < CNT) {
+    const int m = threadIdx.x;
+    dst[LO + m] = (red[m] + red[CNT + m]) + (red[2 * CNT + m] + red[3 * CNT + m]);
+  }
+}
+
+// grid (2 row blocks, jn, T): blockIdx.x = 2 b + slice
+template <int PB>
+__global__ __launch_bounds__(256) void lrx_project_kernel(const float *__restrict__ xt, const float *__restrict__ V,
+                                                          double *__restrict__ part, int N, int T, int j0, int jn) {
+  static_assert(PB > 64 && PB <= 128 && PB % 8 == 0, "the ranks above lr_project_kernel's");
+  __shared__ double red[4 * 64];
+  const int b = blockIdx.x >> 1, slice = blockIdx.x & 1, jj = blockIdx.y, t = blockIdx.z;
+  const float *x = xt + (size_t)(j0 + jj) * N;
+  const int r0 = b * kProjRows + (int)threadIdx.x;
+  float xv[kProjRowsPerThread], vv[kProjRowsPerThread];
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {          // every load requested before the first use, as lr_project_kernel
+    const int i = r0 + u * 256, ic = i < N ? i : N - 1;
+    xv[u] = x[ic];
+    vv[u] = V[(size_t)ic * T + t];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  double *dst = part + (((size_t)b * jn + jj) * T + t) * PB;
+  if (slice == 0)
+    lrx_project_slice<0, 64, PB>(xv, vv, r0, N, red, dst);
+  else
+    lrx_project_slice<64, PB - 64, PB>(xv, vv, r0, N, red, dst);
+}
+
+// (c) of the product: lr_output_kernel's loads, LDS staging and group order with the Clenshaw recurrence in float64.  The
+// rounding of a float32 recurrence grows with the degree (and with its square near |x| = 1), which ranks above 64 — half-widths
+// above 7, where the float32 coordinate itself is already coarse — do not leave room for; U stays float32 in LDS (32 KB at PB
+// 128) and is widened as it is read.  grid (row blocks of 64, T)
+template <int PB>
+__global__ __launch_bounds__(256) void lrx_output_kernel(const float *__restrict__ xt, const float *__restrict__ U,
+                                                         const float *__restrict__ V, float *__restrict__ out, int N, int T,
+                                                         int j0, int jn, int r0, int r1, float noise) {
+  static_assert(PB > 64 && PB <= 128 && PB % 8 == 0, "the ranks above lr_output_kernel's");
+  __shared__ __attribute__((aligned(16))) float su[kPrepMaxJ * PB];
+  __shared__ double sacc[4][kOutRows];
+  const int t = blockIdx.y;
+  const int r = threadIdx.x & (kOutRows - 1), g = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
+  const int i = blockIdx.x * kOutRows + r;
+  const bool mine = i >= r0 && i < r1;
+  int ic = i > r0 ? i : r0;
+  ic = ic < r1 ? ic : r1 - 1;
+  ic = ic < N ? ic : N - 1;
+  ic = ic > 0 ? ic : 0;
+  constexpr int kMaxPer = kPrepMaxJ / 4;
+  float xv[kMaxPer];
+#pragma unroll
+  for (int q = 0; q < kMaxPer; ++q) {
+    const int jj = g + 4 * q;
+    xv[q] = jj < jn ? xt[(size_t)(j0 + jj) * N + ic] : 0.f;
+  }
+  float vn = 0.f;
+  if (g == 0 && noise != 0.f) vn = V[(size_t)(i < N ? i : N - 1) * T + t];
+  constexpr int kTrips = (kPrepMaxJ * PB / 4 + 255) / 256;
+  const int nu4 = jn * (PB / 4);                          // U[.][t][.] of the jn projections as float4
+  float4v uv[kTrips];
+#pragma unroll
+  for (int k = 0; k < kTrips; ++k)
+    if (g * kOutRows + 256 * k < nu4) {
+      const int e = (int)threadIdx.x + 256 * k, ec = e < nu4 ? e : nu4 - 1;
+      uv[k] = *reinterpret_cast<const float4v *>(U + ((size_t)(ec / (PB / 4)) * T + t) * PB + 4 * (ec % (PB / 4)));
+    }
+  __builtin_amdgcn_sched_barrier(0);                      // (every load above is in flight before the first wait)
+#pragma unroll
+  for (int k = 0; k < kTrips; ++k)
+    if (g * kOutRows + 256 * k < nu4) {
+      const int e = (int)threadIdx.x + 256 * k;
+      if (e < nu4) *reinterpret_cast<float4v *>(su + 4 * e) = uv[k];
+    }
+  __syncthreads();
+  double acc = 0.0;
+#pragma unroll
+  for (int q = 0; q < kMaxPer; q += 2) {                  // two projections at a time: two independent float64 chains
+    const int jj = g + 4 * q;
+    if (jj >= jn) break;
+    const bool two = jj + 4 < jn;                         // (wave-uniform; a missing second one re-reads the first's U)
+    const float *u = su + jj * PB, *w = su + (two ? jj + 4 : jj) * PB;
+    const double x = (double)xv[q], x2 = 2.0 * x, y = (double)xv[q + 1], y2 = 2.0 * y;
+    double b1 = 0.0, b2 = 0.0, c1 = 0.0, c2 = 0.0;        // Clenshaw: b_k = U_k + 2x b_{k+1} - b_{k+2}
+#pragma unroll 8
+    for (int k = PB - 1; k >= 1; --k) {
+      const double bk = __builtin_fma(x2, b1, (double)u[k] - b2), ck = __builtin_fma(y2, c1, (double)w[k] - c2);
+      b2 = b1;
+      b1 = bk;
+      c2 = c1;
+      c1 = ck;
+    }
+    acc += __builtin_fma(x, b1, (double)u[0] - b2);
+    if (two) acc += __builtin_fma(y, c1, (double)w[0] - c2);
+  }
+  sacc[g][r] = acc;
+  __syncthreads();
+  if (g != 0 || i >= N) return;
+  double res = mine ? (sacc[0][r] + sacc[1][r]) + (sacc[2][r] + sacc[3][r]) : 0.0;
+  if (noise != 0.f) res = __builtin_fma((double)noise, (double)vn, res);
+  out[(size_t)i * T + t] = (float)res;
+}
+
+template <int PB>
+int launch_lowrank_wide(const LowrankPlan &P, const float *w, const float *V, float *out, int N, int T, int j0, int jn,
+                        int r0, int r1, float scale, float noise, double *part, float *U, hipStream_t st) {
+  const int nblk = proj_blocks(N);
+  hipLaunchKernelGGL(lrx_project_kernel<PB>, dim3(2 * nblk, jn, T), dim3(256), 0, st, P.xt, V, part, N, T, j0, jn);
+  if (w)
+    hipLaunchKernelGGL(lrw_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, w + j0, U, nblk, T, jn, scale);
+  else
+    hipLaunchKernelGGL(lr_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, U, nblk, T, jn, scale);
+  hipLaunchKernelGGL(lrx_output_kernel<PB>, dim3((N + kOutRows - 1) / kOutRows, T), dim3(256), 0, st, P.xt, U, V, out, N, T,
+                     j0, jn, r0, r1, noise);
+  return (int)hipGetLastError();
+}
+
+// (b) of the derivative for PB > 64: lrg_combine_kernel / lrgw_combine_kernel (wt: the weight of projection j0, or null) with
+// the padded ranks as arguments — a latency chain of one workgroup per (projection, t), which 136 (PB, QB) pairs of each
+// kernel would compile for nothing.  Same order of every addition as the templated kernels: G = 256 / pb groups over the row
+// blocks, then the groups in ascending order.  D is exactly antisymmetric, so thread m reads d_km (consecutive in m) and
+// subtracts where lrg_combine_kernel reads row m and adds: the same products, signs and order.
+__global__ __launch_bounds__(256) void lrgx_combine_kernel(const double *__restrict__ partL, const double *__restrict__ partR,
+                                                           const double *__restrict__ dcoef, const double *__restrict__ ccoef,
+                                                           const float *__restrict__ wt, double *__restrict__ U,
+                                                           double *__restrict__ gsp, int nblk, int T, int jn, int p, int pc,
+                                                           int pb, int qb, double scale) {
+  __shared__ double sw[2][256];
+  __shared__ double w[2][128];
+  __shared__ double cw[128];
+  const int G = 256 / pb;
+  const int jj = blockIdx.x, t = blockIdx.y;
+  const int n = threadIdx.x % pb, g = threadIdx.x / pb;
+  const double sj = wt ? scale * (double)wt[jj] : scale;
+  if (g < G) {
+    double sl = 0.0, sr = 0.0;
+    for (int b = g; b < nblk; b += G) {
+      const size_t o = (((size_t)b * jn + jj) * T + t) * pb + n;
+      sl += partL[o];
+      sr += partR[o];
+    }
+    sw[0][g * pb + n] = sl;
+    sw[1][g * pb + n] = sr;
+  }
+  __syncthreads();
+  const int m = threadIdx.x;
+  if (m < pb) {
+    double sl = sw[0][m], sr = sw[1][m];
+    for (int k = 1; k < G; ++k) {
+      sl += sw[0][k * pb + m];
+      sr += sw[1][k * pb + m];
+    }
+    w[0][m] = sl;
+    w[1][m] = sr;
+  }
+  __syncthreads();
+  if (m < qb) {
+    double ur = 0.0, ul = 0.0;
+#pragma unroll 8
+    for (int k = 0; k < qb; ++k) {
+      const double d = -dcoef[k * qb + m];                // = d_mk
+      ur = __builtin_fma(d, w[1][k], ur);
+      ul = __builtin_fma(d, w[0][k], ul);
+    }
+    double *u = U + ((size_t)jj * T + t) * 2 * qb;
+    u[m] = sj * ur;
+    u[qb + m] = sj * ul;
+  }
+  if (m < pb) {                                           // (C W^R)[m], zero beyond p
+    double s = 0.0;
+    if (m < p)
+      for (int k = 0; k < p; ++k) s = __builtin_fma(ccoef[m * pc + k], w[1][k], s);
+    cw[m] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < p; ++k) s = __builtin_fma(w[0][k], cw[k], s);
+    gsp[(size_t)jj * T + t] = s;
+  }
+}
+
+// (c) of the derivative for QB > 64: lrg_output_kernel / lrgw_output_kernel (per_comp) with the Clenshaw sum split at 64.
+// Clenshaw consumes q_k in descending k, so L and R are folded into the upper QB - 64 values first, the recurrence runs down to
+// k = 64, the lower 64 values are folded into the same registers, and the recurrence continues with its (b1, b2): at most 64
+// q per lane, lrg_output_kernel<64>'s footprint, for one more read of the lane's T values of L and R.  grid (row blocks of 64)
+template <int QB>
+__global__ __launch_bounds__(256) void lrgx_output_kernel(const float *__restrict__ xt, const double *__restrict__ U,
+                                                          const double *__restrict__ gsp, const float *__restrict__ L,
+                                                          const float *__restrict__ R, float *__restrict__ gZ,
+                                                          float *__restrict__ gout, int N, int T, int j0, int jn, int ldg,
+                                                          int per_comp) {
+  static_assert(QB > 64 && QB <= 128 && QB % 8 == 0, "the ranks above lrg_output_kernel's");
+  constexpr int HI = QB - 64;
+  __shared__ float sres[kOutRows][kPrepMaxJ + 1];
+  const int r = threadIdx.x & (kOutRows - 1);
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
+  const int row0 = blockIdx.x * kOutRows;
+  const int i = row0 + r;
+  const bool ok = i < N;
+  for (int jj = wv; jj < jn; jj += 4) {
+    const double *u = U + (size_t)jj * T * 2 * QB;
+    const double x = ok ? (double)xt[(size_t)(j0 + jj) * N + i] : 0.0, x2 = 2.0 * x;
+    double q[64];
+#pragma unroll
+    for (int m = 0; m < HI; ++m) q[m] = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const double l = ok ? (double)L[(size_t)i * T + t] : 0.0;
+      const double rr = ok ? (double)R[(size_t)i * T + t] : 0.0;
+      const double *ut = u + (size_t)t * 2 * QB + 64;
+#pragma unroll
+      for (int m = 0; m < HI; ++m) q[m] = __builtin_fma(l, ut[m], __builtin_fma(rr, ut[QB + m], q[m]));
+    }
+    double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = HI - 1; k >= 0; --k) {                   // ranks QB - 1 ... 64
+      const double bk = __builtin_fma(x2, b1, q[k] - b2);
+      b2 = b1;
+      b1 = bk;
+    }
+    asm volatile("" : "+v"(b1), "+v"(b2));                // (the upper sum ends here: its q are dead before the lower fold)
+#pragma unroll
+    for (int m = 0; m < 64; ++m) q[m] = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const double l = ok ? (double)L[(size_t)i * T + t] : 0.0;
+      const double rr = ok ? (double)R[(size_t)i * T + t] : 0.0;
+      const double *ut = u + (size_t)t * 2 * QB;
+#pragma unroll
+      for (int m = 0; m < 64; ++m) q[m] = __builtin_fma(l, ut[m], __builtin_fma(rr, ut[QB + m], q[m]));
+    }
+#pragma unroll
+    for (int k = 63; k >= 1; --k) {
+      const double bk = __builtin_fma(x2, b1, q[k] - b2);
+      b2 = b1;
+      b1 = bk;
+    }
+    sres[r][jj] = (float)__builtin_fma(x, b1, q[0] - b2);
+  }
+  __syncthreads();
+  const int rows = N - row0 < kOutRows ? N - row0 : kOutRows;
+  for (int e = threadIdx.x; e < rows * jn; e += 256) {
+    const int rr = e / jn, c = e - rr * jn;
+    gZ[(size_t)(row0 + rr) * ldg + j0 + c] = sres[rr][c];
+  }
+  if (blockIdx.x != 0) return;
+  if (per_comp) {                                         // gcomp[j0 + jj] = sum_t gsp[jj][t], as lrgw_output_kernel
+    if ((int)threadIdx.x < jn) {
+      double s = 0.0;
+      for (int t = 0; t < T; ++t) s += gsp[(size_t)threadIdx.x * T + t];
+      gout[j0 + threadIdx.x] = (float)s;
+    }
+  } else if (threadIdx.x == 0) {                          // gscale, as lrg_output_kernel
+    double s = 0.0;
+    for (int k = 0; k < jn * T; ++k) s += gsp[k];
+    *gout = (float)s;
+  }
+}
+
+// the derivative with PB = pad8(max(p, q)) > 64; w: the weights (gout = gcomp, ldg = J) or null (gout = gscale).  QB <= 64
+// (p > 64 >= q) runs the output kernels above.
+template <int PB>
+void launch_grad_wide_project(const LowrankPlan &P, const float *L, const float *R, double *partL, double *partR, int N, int T,
+                              int j0, int jn, hipStream_t st) {
+  const int nblk = proj_blocks(N);
+  hipLaunchKernelGGL(lrx_project_kernel<PB>, dim3(2 * nblk, jn, T), dim3(256), 0, st, P.xt, L, partL, N, T, j0, jn);
+  hipLaunchKernelGGL(lrx_project_kernel<PB>, dim3(2 * nblk, jn, T), dim3(256), 0, st, P.xt, R, partR, N, T, j0, jn);
+}
+
+template <int QB>
+void launch_grad_wide_output(const LowrankPlan &P, const float *w, const double *U, const double *gsp, const float *L,
+                             const float *R, float *gZ, float *gout, int N, int T, int j0, int jn, int ldg, hipStream_t st) {
+  const dim3 grid((N + kOutRows - 1) / kOutRows);
+  if constexpr (QB > 64)
+    hipLaunchKernelGGL(lrgx_output_kernel<QB>, grid, dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gout, N, T, j0, jn, ldg,
+                       w ? 1 : 0);
+  else if (w)
+    hipLaunchKernelGGL(lrgw_output_kernel<QB>, grid, dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gout, N, T, j0, jn, ldg);
+  else
+    hipLaunchKernelGGL(lrg_output_kernel<QB>, grid, dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gout, N, T, j0, jn, ldg);
+}
+
 // ---- explicit features of the posterior (rpgp_lowrank_post_select / rpgp_lowrank_features_f64) --------------------------
 // C (p x p, symmetric PSD up to rounding: a congruence of the kernel's Gram matrix at the Chebyshev points) = Q diag(l) Q^T by
 // cyclic Jacobi rotations in double (a fixed sweep order: deterministic).  a: p x p row-major, overwritten; q: eigenvectors as
@@ -1020,7 +1359,7 @@ typedef double double4v __attribute__((ext_vector_type(4)));
 //   PB  72:  80 | 112      PB  80:  84 | 116      PB  88:  88 | 120      PB  96:  92 | 124
 //   PB 104:  96 | 128      PB 112: 100 | 132      PB 120: 104 | 136      PB 128: 108 | 140
 // so registers allow 3 waves per SIMD at worst and above PB 64 LDS is what bounds the occupancy.
-constexpr int kFeatMaxRank = 128;        // largest p (and r) of the feature kernels; the float32 product kernels keep kMaxRank
+constexpr int kFeatMaxRank = 128;        // largest p (and r) of the feature kernels
 constexpr int wide_ld(int nct) { return ((nct * 16 + 31) & ~31) + 16; }           // 48, 48, 80, 80, 112, 112, 144, 144
 constexpr size_t wide_lds_bytes(int pb, int nct) { return (size_t)pb * wide_ld(nct) * sizeof(double); }
 
@@ -1299,24 +1638,25 @@ int select_to_host(double h, int p_max, double tol, bool deriv, int *p_host, dou
 
 // the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
 int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes, int *p_host,
-                void **handle_host, void *stream) {
+                void **handle_host, void *stream, int cap = kMaxRank) {
   if (!prep || !plan || !p_host || !handle_host || N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ)
     return RPGP_EINVAL;
-  if (plan_bytes < rpgp_lowrank_plan_bytes(N, J)) return RPGP_EWORKSPACE;
+  if (plan_bytes < rpgp_lowrank_plan_bytes_cap(N, J, cap)) return RPGP_EWORKSPACE;
   *p_host = 0;
   *handle_host = nullptr;
   // a slightly wider interval than max|a| absorbs the rounding of a = (z - mid) * c at the ends of the range
   const double h = (double)max_abs * (1.0 + 1.0 / (1 << 20));
   std::vector<double> c;
   double tail = 0.0;
-  const int p = select_rank(h, kMaxRank, tol, &tail, c);
+  const int p = select_rank(h, cap, tol, &tail, c);
   if (p == 0) return 0;                                   // not served: the sweep runs
   const int pb = pad8(p);
   std::vector<float> cf((size_t)pb * pb, 0.f);
   copy_leading_block(c, p, cf.data(), pb);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float *coef = reinterpret_cast<float *>(plan);
-  float *xt = coef + (size_t)kMaxRank * kMaxRank;
+  const int ld = cap_ld(cap);
+  float *xt = coef + (size_t)ld * ld;
   hipError_t e = hipMemcpyAsync(coef, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return (int)e;
   // (rank 1: T_0 = 1 whatever x is; h = 0 would divide by zero)
@@ -1332,9 +1672,34 @@ int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, v
   LowrankPlan *P = new (std::nothrow) LowrankPlan{p, pb, N, J, h, tail, coef, xt};
   if (!P) return RPGP_EINVAL;
   P->tol = tol;
+  P->cap = cap;
+  P->ld = ld;
   *p_host = p;
   *handle_host = P;
   return 0;
+}
+
+// the derivative of a plan with pad8(max(p, q)) > 64: the projections by padded rank, the combine with the ranks as arguments,
+// the output by QB.  w: the weights (gout = gcomp) or null (gout = gscale).  Same workspace layout as launch_grad.
+int launch_grad_wide(const LowrankPlan &P, const float *w, const float *L, const float *R, float *gZ, float *gout, int N,
+                     int ldg, int T, int j0, int jn, float scale, void *ws, hipStream_t st) {
+  const int nblk = proj_blocks(N), pb = grad_pb(P), qb = P.qb;
+  const size_t np = (size_t)nblk * jn * T * pb;
+  double *partL = reinterpret_cast<double *>(ws), *partR = partL + np;
+  double *U = partR + np, *gsp = U + (size_t)jn * T * 2 * qb;
+  int rc = dispatch_pb<kCapRank, kMaxRank + 8>(pb, [&](auto b) {
+    launch_grad_wide_project<decltype(b)::value>(P, L, R, partL, partR, N, T, j0, jn, st);
+    return (int)hipGetLastError();
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(lrgx_combine_kernel, dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, w ? w + j0 : nullptr, U,
+                     gsp, nblk, T, jn, P.p, P.pb, pb, qb, (double)scale);
+  rc = (int)hipGetLastError();
+  if (rc) return rc;
+  return dispatch_pb<kCapRank>(qb, [&](auto b) {
+    launch_grad_wide_output<decltype(b)::value>(P, w, U, gsp, L, R, gZ, gout, N, T, j0, jn, ldg, st);
+    return (int)hipGetLastError();
+  });
 }
 
 }  // namespace
@@ -1345,9 +1710,24 @@ int rpgp_lowrank_select(double h, int p_max, int *p_host, double *tail_host, dou
   return select_to_host(h, p_max, kTailTol, false, p_host, tail_host, coef_host);
 }
 
-size_t rpgp_lowrank_plan_bytes(int64_t N, int J) {
-  if (N <= 0 || J <= 0 || J > kPrepMaxJ) return 0;
-  return ((size_t)kMaxRank * kMaxRank + (size_t)N * J) * sizeof(float);
+size_t rpgp_lowrank_plan_bytes(int64_t N, int J) { return rpgp_lowrank_plan_bytes_cap(N, J, kMaxRank); }
+
+size_t rpgp_lowrank_plan_bytes_cap(int64_t N, int J, int p_max) {
+  if (N <= 0 || J <= 0 || J > kPrepMaxJ || p_max < 1 || p_max > kCapRank) return 0;
+  const size_t ld = cap_ld(p_max);
+  return (ld * ld + (size_t)N * J) * sizeof(float);
+}
+
+int rpgp_lowrank_create_cap(const void *prep, int64_t N, int J, float max_abs, double tol, int p_max, void *plan,
+                            size_t plan_bytes, int *p_host, void **handle_host, void *stream) {
+  if (!(tol > 0.0) || p_max < 1 || p_max > kCapRank) return RPGP_EINVAL;
+  return create_plan(prep, N, J, max_abs, tol < kTailTol ? tol : kTailTol, plan, plan_bytes, p_host, handle_host, stream, p_max);
+}
+
+size_t rpgp_lowrank_grad_bytes(const void *handle) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P) return 0;
+  return (size_t)2 * P->ld * P->ld * sizeof(double);      // D and C (64: RPGP_LOWRANK_GRAD_BYTES)
 }
 
 int rpgp_lowrank_create(const void *prep, int64_t N, int J, float max_abs, void *plan, size_t plan_bytes, int *p_host,
@@ -1389,8 +1769,12 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
   double *part = reinterpret_cast<double *>(workspace);
   float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
   const bool prof = rpgp_internal::prof_open(st);
-  int rc = dispatch_pb<kMaxRank>(P->pb, [&](auto pb) {
-    return launch_lowrank<decltype(pb)::value>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st);
+  int rc = dispatch_pb<kCapRank>(P->pb, [&](auto pb) {
+    constexpr int PB = decltype(pb)::value;
+    if constexpr (PB <= kMaxRank)
+      return launch_lowrank<PB>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st);
+    else
+      return launch_lowrank_wide<PB>(*P, nullptr, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st);
   });
   if (prof) {
     const int pc = rpgp_internal::prof_close(st);
@@ -1406,23 +1790,24 @@ int rpgp_lowrank_grad_select(double h, int q_max, double tol, int *q_host, doubl
 int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoef_bytes, int *q_host, void *stream) {
   LowrankPlan *P = reinterpret_cast<LowrankPlan *>(handle);
   if (!P || !dcoef || !q_host || !(tol > 0.0)) return RPGP_EINVAL;
-  if (dcoef_bytes < (size_t)RPGP_LOWRANK_GRAD_BYTES) return RPGP_EWORKSPACE;
+  if (dcoef_bytes < rpgp_lowrank_grad_bytes(handle)) return RPGP_EWORKSPACE;
   *q_host = 0;
   P->q = P->qb = 0;
   P->dcoef = nullptr;
   std::vector<double> c;
   double tail = 0.0;
-  const int q = select_rank(P->h, kMaxRank, tol < kTailTol ? tol : kTailTol, &tail, c, true);
+  const int q = select_rank(P->h, P->cap, tol < kTailTol ? tol : kTailTol, &tail, c, true);
   // (a rank-1 plan stores x = 0: it cannot evaluate a derivative of rank > 1)
   if (q == 0 || (P->p == 1 && q > 1)) return 0;
   const int qb = pad8(q);
-  // [D: qb x qb][C: pb x pb at 32 KiB], both float64; C is the plan's own selection again (same h, tolerance: same p)
+  // [D: qb x qb][C: pb x pb at ld x ld doubles: 32 KiB for ld = 64], both float64; C is the plan's own selection again (same h,
+  // tolerance and cap: same p)
   std::vector<double> d((size_t)qb * qb, 0.0), cc((size_t)P->pb * P->pb, 0.0), cf;
   copy_leading_block(c, q, d.data(), qb);
-  if (select_rank(P->h, kMaxRank, P->tol, nullptr, cf) != P->p) return RPGP_EINVAL;
+  if (select_rank(P->h, P->cap, P->tol, nullptr, cf) != P->p) return RPGP_EINVAL;
   copy_leading_block(cf, P->p, cc.data(), P->pb);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  double *dd = reinterpret_cast<double *>(dcoef), *dc = dd + kMaxRank * kMaxRank;
+  double *dd = reinterpret_cast<double *>(dcoef), *dc = dd + (size_t)P->ld * P->ld;
   hipError_t e = hipMemcpyAsync(dd, d.data(), d.size() * sizeof(double), hipMemcpyHostToDevice, st);
   if (e != hipSuccess) return (int)e;
   e = hipMemcpyAsync(dc, cc.data(), cc.size() * sizeof(double), hipMemcpyHostToDevice, st);
@@ -1453,6 +1838,8 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
   if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int n = (int)N, jn = j1 - j0;
+  if (grad_pb(*P) > kMaxRank)
+    return launch_grad_wide(*P, nullptr, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st);
   // (PB < QB never occurs: PB = pad8(max(p, q)) >= QB, so no such kernel is instantiated)
   return dispatch_pb<kMaxRank>(P->qb, [&](auto qb) {
     return dispatch_pb<kMaxRank>(grad_pb(*P), [&](auto pb) -> int {
@@ -1479,8 +1866,12 @@ int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const fl
   double *part = reinterpret_cast<double *>(workspace);
   float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
   const bool prof = rpgp_internal::prof_open(st);
-  int rc = dispatch_pb<kMaxRank>(P->pb, [&](auto pb) {
-    return launch_lowrank_weighted<decltype(pb)::value>(*P, weights, V, out, n, T, j0, jn, scale, noise, part, U, st);
+  int rc = dispatch_pb<kCapRank>(P->pb, [&](auto pb) {
+    constexpr int PB = decltype(pb)::value;
+    if constexpr (PB <= kMaxRank)
+      return launch_lowrank_weighted<PB>(*P, weights, V, out, n, T, j0, jn, scale, noise, part, U, st);
+    else
+      return launch_lowrank_wide<PB>(*P, weights, V, out, n, T, j0, jn, 0, n, scale, noise, part, U, st);
   });
   if (prof) {
     const int pc = rpgp_internal::prof_close(st);
@@ -1499,6 +1890,8 @@ int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights
   if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int n = (int)N, jn = j1 - j0;
+  if (grad_pb(*P) > kMaxRank)
+    return launch_grad_wide(*P, weights, L, R, gZ, gcomp, n, P->J, T, j0, jn, scale, workspace, st);
   return dispatch_pb<kMaxRank>(P->qb, [&](auto qb) {
     return dispatch_pb<kMaxRank>(grad_pb(*P), [&](auto pb) -> int {
       constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;

@@ -186,7 +186,8 @@ class AdditiveRPOperator(LinearOperator):
         """The training plan of the Chebyshev low-rank form that serves this operator's solves and derivative
         (settings.lowrank_kernel), or None for the exact sweep.  Decided ONCE per operator (= per hyper-parameter step) from
         N, the scale and the noise (default: the host value the marginal likelihood recorded), so that the solve and the
-        derivative of a step use the same form."""
+        derivative of a step use the same form.  Ranks p, q up to settings.lowrank_max_rank (64 by default; above it a Z
+        beyond the factorised sweep's range guard is served too, and its Python-path products run the direct sweep)."""
         if getattr(self, "_lowrank", None) is None:
             self._lowrank = False
             be = _backend.get_backend()
@@ -198,7 +199,8 @@ class AdditiveRPOperator(LinearOperator):
                     plan_fn is not None and prepare is not None and noise is not None and self.num_projections <= 64:
                 if self._prep is None:
                     self._prep = prepare(self.Z1.detach())
-                plan = plan_fn(self._prep, self._scale, float(noise))
+                cap = settings.lowrank_max_rank.value()     # (passed on only above the default: 64 is the plan's own)
+                plan = plan_fn(self._prep, self._scale, float(noise), **({"max_rank": cap} if cap > 64 else {}))
                 if plan is not None:
                     self._lowrank = plan
         return self._lowrank or None
@@ -833,7 +835,7 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         column of Z (the lengthscales are folded into the columns; a component weight is a factor of the combine pass) that
         serves this operator's solves and derivative under settings.lowrank_kernel, or None for the family sweep.  Served: a
         symmetric float32 RBF operator with k = 1 and J <= 64, a backend with the weighted entries, a known positive noise and
-        a plan with p, q <= 64 at the tolerance of the kernel's diagonal mass scale * sum_c |w_c| (weights of any sign: the
+        a plan with p, q <= settings.lowrank_max_rank (64 by default) at the tolerance of the kernel's diagonal mass scale * sum_c |w_c| (weights of any sign: the
         product is linear in them).  Decided ONCE per operator, like the plain operator's."""
         if getattr(self, "_lowrank", None) is None:
             self._lowrank = False
@@ -848,9 +850,11 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
                     noise is not None and float(noise) > 0.0:
                 if self._prep is None:
                     self._prep = prepare(self.Z1.detach())
-                if self._prep.fast_ok:
+                cap = settings.lowrank_max_rank.value()     # (passed on only above the default: 64 is the plan's own)
+                if self._prep.fast_ok or cap > 64:          # (above 64 the plan decides: a finite range, not the sweep's guard)
                     wabs = float(self.fam.weights.abs().sum())
-                    plan = plan_fn(self._prep, self._scale, float(noise), mass=self._scale * wabs)
+                    plan = plan_fn(self._prep, self._scale, float(noise), mass=self._scale * wabs,
+                                   **({"max_rank": cap} if cap > 64 else {}))
                     if plan is not None:
                         self._lowrank = plan
         return self._lowrank or None

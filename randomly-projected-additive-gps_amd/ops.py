@@ -280,16 +280,52 @@ def lowrank_grad_select(h, q_max=64, tol=_LOWRANK_TAIL):
     return q, float(tail.value), D[:q, :q].copy()
 
 
+LOWRANK_KERNEL_RANK = 128       # largest rank cap of a LowrankTrainPlan (rpgp_lowrank_create_cap)
+
+
 class LowrankTrainPlan:
     """Training plan of one Prepared (rpgp_lowrank_create_tol + rpgp_lowrank_grad_prepare at one tolerance): the product
-    (RPGP_OP_LOWRANK) and the derivative (rpgp_bilinear_grad_lowrank) of the same low-rank form.  p, q: ranks (0: not served)."""
+    (RPGP_OP_LOWRANK) and the derivative (rpgp_bilinear_grad_lowrank) of the same low-rank form.  p, q: ranks (0: not served).
+    `max_rank`: the largest p and q served; 64 is rpgp_lowrank_create_tol's plan, above it (up to 128) the plan comes from
+    rpgp_lowrank_create_cap with its buffers sized for the cap, and needs a prepared buffer with a finite max_abs."""
 
-    def __init__(self, prep, tol):
+    def __init__(self, prep, tol, max_rank=64):
         import ctypes
+        import math
         lib = _lib.load()
+        max_rank = int(max_rank)
+        if not 1 <= max_rank <= LOWRANK_KERNEL_RANK:
+            raise ValueError("LowrankTrainPlan: max_rank = %r outside 1 ... %d" % (max_rank, LOWRANK_KERNEL_RANK))
         self.N, self.J, self.device, self.tol = prep.N, prep.J, prep.device, float(tol)
+        self.max_rank = max_rank
         self.p = self.q = 0
         self.handle = None
+        if max_rank > 64:
+            if prep.buf is None or not math.isfinite(prep.max_abs):
+                return                                    # no prepared coordinates, or a Z with an Inf: not served
+            if not prep.fast_ok:
+                # beyond the sweep's range guard, or a NaN (which max_abs skips): the prepared coordinates decide, one
+                # reduction and one host sync per plan (rowdat: N J float2 behind the 128-float header)
+                rowdat = prep.buf[512:512 + 8 * self.N * self.J].view(torch.float32)
+                if not bool(torch.isfinite(rowdat).all()):
+                    return
+            with _on(prep.device):
+                self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes_cap(self.N, self.J, max_rank)), dtype=torch.uint8,
+                                         device=self.device)
+                p, h = ctypes.c_int(0), ctypes.c_void_p(None)
+                _lib.check(lib.rpgp_lowrank_create_cap(prep.buf.data_ptr(), self.N, self.J, prep.max_abs, self.tol, max_rank,
+                                                       self._plan.data_ptr(), self._plan.numel(), ctypes.byref(p),
+                                                       ctypes.byref(h), _stream()), "rpgp_lowrank_create_cap")
+                self.p, self.handle = int(p.value), h.value
+                if self.p:
+                    self._dcoef = torch.empty(int(lib.rpgp_lowrank_grad_bytes(self.handle)), dtype=torch.uint8,
+                                              device=self.device)
+                    q = ctypes.c_int(0)
+                    _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(),
+                                                             self._dcoef.numel(), ctypes.byref(q), _stream()),
+                               "rpgp_lowrank_grad_prepare")
+                    self.q = int(q.value)
+            return
         with _on(prep.device):
             self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes(self.N, self.J)), dtype=torch.uint8, device=self.device)
             p, h = ctypes.c_int(0), ctypes.c_void_p(None)
@@ -314,19 +350,27 @@ class LowrankTrainPlan:
             self.handle = None
 
 
-def lowrank_train_plan(prep, scale, noise, mass=None):
+def lowrank_train_plan(prep, scale, noise, mass=None, max_rank=64):
     """The training plan of `prep` for this step's (N, scale, noise), or None when the low-rank form does not serve it (switch
-    off, not fast_ok, no tolerance, or p or q above 64).  Built once per Prepared and tolerance.  `mass`: the kernel's diagonal
-    mass when it is not scale * J — scale * sum_c |w_c| of a weighted family operator, so that lowrank_train_tol's spectral
-    bound holds for it."""
-    if not lowrank_enabled() or not prep.fast_ok:
+    off, no tolerance, p or q above max_rank; at max_rank 64 a Z that is not fast_ok, above it one without prepared coordinates
+    or with a non-finite max_abs: the Chebyshev form evaluates no exponential, so the sweep's exp2 range guard does not bind
+    it).  Built once per Prepared, tolerance and cap.  `mass`: the kernel's diagonal mass when it is not scale * J — scale *
+    sum_c |w_c| of a weighted family operator, so that lowrank_train_tol's spectral bound holds for it."""
+    import math
+    max_rank = int(max_rank)
+    if not lowrank_enabled():
+        return None
+    if max_rank <= 64:
+        if not prep.fast_ok:
+            return None
+    elif prep.buf is None or not math.isfinite(prep.max_abs):
         return None
     tol = lowrank_train_tol(prep.N, prep.J, scale, noise) if mass is None else lowrank_train_tol(prep.N, 1, mass, noise)
     if not tol:
         return None
     cached = getattr(prep, "_train", None)
-    if cached is None or cached.tol != tol:
-        cached = prep._train = LowrankTrainPlan(prep, tol)
+    if cached is None or cached.tol != tol or getattr(cached, "max_rank", 64) != max_rank:
+        cached = prep._train = LowrankTrainPlan(prep, tol) if max_rank == 64 else LowrankTrainPlan(prep, tol, max_rank)
     return cached if cached.served else None
 
 

@@ -254,7 +254,7 @@ def build_parser():
     p.add_argument("--lowrank_mll", action="store_true",
                    help="(rpgp) train on the closed-form marginal likelihood of the Chebyshev low-rank features where served")
     p.add_argument("--lowrank_max_rank", type=int, default=64, metavar="N",
-                   help="(rpgp) largest Chebyshev rank served by --lowrank_posterior / --lowrank_mll (1 ... 128, default 64)")
+                   help="(rpgp) largest Chebyshev rank served by --lowrank_kernel / --lowrank_posterior / --lowrank_mll (1 ... 128, default 64)")
     return p
 
 

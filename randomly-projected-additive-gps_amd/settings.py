@@ -134,7 +134,7 @@ comm_backend = _setting("comm_backend", "rccl")
 native_sharded_cg = _setting("native_sharded_cg", True, flag=True)
 # training and its solves on the Chebyshev low-rank form of the exact kernel (csrc/rpgp_lowrank.hip): an unsharded float32
 # additive-RP operator whose plan at the training tolerance (per-entry tail <= min(2^-26, 1e-3 noise / (scale J N))) has ranks
-# p, q <= 64 is solved through RPGP_OP_LOWRANK (no packed / dense cache) and differentiated by rpgp_bilinear_grad_lowrank — both
+# p, q <= lowrank_max_rank (64 by default, up to 128) is solved through RPGP_OP_LOWRANK (no packed / dense cache) and differentiated by rpgp_bilinear_grad_lowrank — both
 # or neither, decided once per operator.  Off: the exact sweep.  RPGP_LOWRANK=0 and RPGP_FACT_ASM keep the sweep either way.
 # The weighted kinds (FamilyAdditiveOperator: RBF, k = 1, one lengthscale and one weight of any sign per projection, J <= 64) are
 # served the same way on the one form shared by every column, at the tolerance of the kernel's diagonal mass
@@ -159,10 +159,13 @@ lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
 lowrank_mll = _setting("lowrank_mll", False, flag=True)
 
 
-# the largest Chebyshev rank p that lowrank_posterior and lowrank_mll serve: 64 covers a half-width of the 1-D term of about 7.3
+# the largest Chebyshev rank that lowrank_posterior, lowrank_mll (p) and lowrank_kernel (p and q) serve: 64 covers a half-width of the 1-D term of about 7.3
 # (tail 1e-10) in the units of exp2(-h^2 (x - y)^2), 128 about 14 (the degree-128 reference resolves no more).  Above 64 the
 # feature kernels stage G in dynamic LDS and the selection uses a tridiagonal eigensolver; at or below 64 nothing changes with
-# this setting, bit for bit.  lowrank_kernel (the float32 product kernels) keeps its own cap of 64.
+# this setting, bit for bit.  lowrank_kernel above 64 builds its plan with rpgp_lowrank_create_cap: padded ranks 72 ... 128 run
+# the rank-sliced projection and the split float64 Clenshaw kernels of csrc/rpgp_lowrank.hip, a plan with p, q <= 64 the kernels
+# (and the bits) of the default cap, and a Z beyond the factorised sweep's range guard (half-width 10 ... about 14) is served
+# as well, since the Chebyshev form evaluates no exponential.  Prepared.rank and the default RPGP_LOWRANK product stay at 64.
 class lowrank_max_rank(_Setting):
     _default = 64
     _value = None

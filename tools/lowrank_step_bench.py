@@ -3,7 +3,8 @@ and derivative of csrc/rpgp_lowrank.hip), on synthetic stand-ins of the BASELINE
 (configuration, setting): the median step time over the timed steps (after warm-up steps), the CG iterations per step, the
 ranks p, q of the training plan and whether the low-rank form served every timed step.  --weighted times the weighted rp_poly
 model instead (k = 1: one lengthscale and one weight per projection, the FamilyAdditiveOperator), with the lengthscales spread
---spread times across the projections."""
+--spread times across the projections.  --max_rank sets settings.lowrank_max_rank for the run (64 by default; up to 128, which
+serves half-widths up to about 13).  The parent of a change is timed by running its own copy of this tool with --modes off."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -65,7 +66,7 @@ def _weighted_model(X, y, J, half_width, spread, dev):
 
 
 def run(name, N, d, J, steps, warmup, on, space_proj, cg_tol, half_width=None, lr=0.1, quiet=False, weighted=False,
-        spread=1.0, tag=None, out=None):
+        spread=1.0, tag=None, out=None, max_rank=64):
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
     X = torch.randn(N, d, generator=g)
@@ -86,13 +87,14 @@ def run(name, N, d, J, steps, warmup, on, space_proj, cg_tol, half_width=None, l
     mll = ExactMarginalLogLikelihood(lik, model)
     opt = make_optimizer(torch.optim.Adam, [p for p in model.parameters() if p.requires_grad], lr)
     res = {"config": name, "N": N, "d": d, "J": J, "lowrank_kernel": on, "steps": steps, "warmup": warmup,
-           "half_width": half_width, "lr": lr, "cg_tol": cg_tol}
+           "half_width": half_width, "lr": lr, "cg_tol": cg_tol, "max_rank": max_rank}
     if weighted:
         res.update(model="rp_poly weighted k=1", spread=spread)
     if tag is not None:
         res["tag"] = tag
     times, iters, losses, served, ranks = [], [], [], [], []
-    with settings.cg_tolerance(cg_tol), settings.max_cg_iterations(10000), settings.lowrank_kernel(on):
+    with settings.cg_tolerance(cg_tol), settings.max_cg_iterations(10000), settings.lowrank_kernel(on), \
+            settings.lowrank_max_rank(max_rank):
         model.train()
         for it in range(warmup + steps):
             _last.clear()
@@ -139,6 +141,8 @@ if __name__ == "__main__":
     ap.add_argument("--lr", type=float, default=0.1)
     ap.add_argument("--weighted", action="store_true", help="the weighted rp_poly model (k = 1) instead of additive_rp")
     ap.add_argument("--spread", type=float, default=1.0, help="--weighted: longest / shortest lengthscale across projections")
+    ap.add_argument("--max_rank", type=int, default=64,
+                    help="settings.lowrank_max_rank: the largest p, q the low-rank form serves (1 ... 128, default 64)")
     ap.add_argument("--tag", default=None, help="a label copied into every record (which run, which build)")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file")
     a = ap.parse_args()
@@ -153,7 +157,7 @@ if __name__ == "__main__":
         name, N, d, J, sp = table[c]
         for m in a.modes.split(","):
             run(name, N, d, J, a.steps, a.warmup, m == "on", sp, a.cg_tol, a.half_width, a.lr, weighted=a.weighted,
-                spread=a.spread, tag=a.tag, out=a.out)
+                spread=a.spread, tag=a.tag, out=a.out, max_rank=a.max_rank)
     # (the preconditioner's library warm-up runs in a helper thread: a run of a few fast steps must not end underneath it)
     from rpgp_amd import precond
     precond.finish_factorisation_warmup()
