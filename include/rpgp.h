@@ -216,6 +216,44 @@ int rpgp_lowrank_create_cap(const void *prep, int64_t N, int J, float max_abs, d
 size_t rpgp_lowrank_grad_bytes(const void *handle);
 
 /*
+ * Panel plans: any half-width at the per-row work of a rank <= 64 plan.  [-h, h] is cut into P equal panels of half-width
+ * hp = h / P (centres c_k = -h + (2k + 1) hp, local coordinate x = (a - c_k) / hp).  Two points of one panel interact through
+ * C0 (rpgp_lowrank_select's form at hp), a point of panel k with one of panel k + 1 through C1, the coefficients of
+ * exp2(-hp^2 (x - y - 2)^2) (x in the lower panel; the opposite order is C1^T), and points two or more panels apart are dropped:
+ * they are at least 2 hp apart.  D0, D1 and -D1^T are the same for the derivative.  The per-entry bound of the product is the
+ * largest of the tail of C0, the tail of C1 and the largest dropped value exp2(-4 hp^2) (0 for P = 2, which drops nothing); the
+ * derivative's is built the same way from D0, D1 and (2 hp / kappa) exp2(-4 hp^2).
+ *   rpgp_lowrank_panels_select (host only, no device): the smallest P in 2 ... rpgp_lowrank_panels_max() (16: half-widths up to
+ *     about 100) — or, for panels > 0, that count alone — for which the four ranks are <= 64 and all six bounds are <=
+ *     min(tol, 2^-26).  *panels_host = 0: none.  p = the larger rank of C0 and C1, q of D0 and D1; bounds_host[3] / dbounds_host[3]
+ *     (optional) = {tail of the same-panel form, tail of the neighbour form, dropped} at those ranks; coef_host (optional):
+ *     [C0][C1][D0][D1], 64 x 64 doubles each, zero outside p x p / q x q.  RPGP_EINVAL for panels = 1 or outside 0 ... 16.
+ *   rpgp_lowrank_panels_plan_bytes: size of the plan buffer for any panel count (0 for N, J outside the limits).
+ *   rpgp_lowrank_create_panels: the plan of that selection at h = max_abs (1 + 2^-20), once per Z after rpgp_prepare, into the
+ *     caller's buffer; *panels_host = *p_host = 0 and *handle_host = NULL when it is not served.  The plan holds C0, C1 (fp32), the
+ *     local coordinate and the panel of every (column, row) in natural order, and for every column the rows in panel order: a
+ *     stable counting sort whose positions are prefix sums (a function of Z alone), every (column, panel) segment padded to whole
+ *     projection blocks of 2 048 slots (a padded slot contributes v = 0), with the first block of every panel per column.  A
+ *     coordinate at +h belongs to the last panel, one exactly on an inner edge to the upper panel.  Like rpgp_lowrank_create_cap
+ *     it does not read fast_ok, and the caller vouches for coordinates without a NaN.  rpgp_lowrank_destroy frees the handle.
+ *   rpgp_lowrank_panels_info: P (0: a single-interval plan), hp, p, q and the product's three bounds of a handle.
+ * Every entry that takes a handle serves a panel plan with the contract stated above: rpgp_mvm_sym_lowrank_range,
+ * rpgp_mvm_sym_lowrank_weighted, rpgp_bilinear_grad_lowrank[_weighted], the two *_workspace_bytes, rpgp_lowrank_grad_bytes
+ * (D0, D1 and the float64 C0, C1: 128 KiB), rpgp_lowrank_grad_prepare (the derivative is selected with the plan, at the plan's
+ * tolerance: *q_host = 0 for a smaller `tol`), rpgp_mbcg_workspace_bytes and the executor's RPGP_OP_LOWRANK /
+ * RPGP_OP_LOWRANK_FAMILY.  No float atomics; repeated calls are bit-identical; a NULL weight pointer and weights of 1 give the
+ * same bits.
+ */
+int rpgp_lowrank_panels_select(double h, double tol, int panels, int *panels_host, double *hp_host, int *p_host, int *q_host,
+                               double *bounds_host, double *dbounds_host, double *coef_host);
+int rpgp_lowrank_panels_max(void);
+size_t rpgp_lowrank_panels_plan_bytes(int64_t N, int J);
+int rpgp_lowrank_create_panels(const void *prep, int64_t N, int J, float max_abs, double tol, int panels, void *plan,
+                               size_t plan_bytes, int *panels_host, int *p_host, void **handle_host, void *stream);
+int rpgp_lowrank_panels_info(const void *handle, int *panels_host, double *hp_host, int *p_host, int *q_host,
+                             double *bounds_host);
+
+/*
  * Explicit features of the truncated kernel (the closed-form posterior of the low-rank form).  Factor C ~= G G^T (G: p x r), so
  * that every 1-D term is exp2(-h^2 (x - y)^2) ~= (G^T T(x))^T (G^T T(y)) and the kernel is K_lr = B B^T with
  * B = sqrt(scale) [T(x_1) G | ... | T(x_J) G]  (N x J r).

@@ -54,6 +54,14 @@ SIGNATURES = {
     "rpgp_lowrank_create_cap": (_int, [_vp, _i64, _int, _f32, _f64, _int, _vp, _sz, ctypes.POINTER(ctypes.c_int),
                                        ctypes.POINTER(_vp), _vp]),
     "rpgp_lowrank_grad_bytes": (_sz, [_vp]),
+    "rpgp_lowrank_panels_select": (_int, [_f64, _f64, _int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double),
+                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _vp, _vp, _vp]),
+    "rpgp_lowrank_panels_max": (_int, []),
+    "rpgp_lowrank_panels_plan_bytes": (_sz, [_i64, _int]),
+    "rpgp_lowrank_create_panels": (_int, [_vp, _i64, _int, _f32, _f64, _int, _vp, _sz, ctypes.POINTER(ctypes.c_int),
+                                          ctypes.POINTER(ctypes.c_int), ctypes.POINTER(_vp), _vp]),
+    "rpgp_lowrank_panels_info": (_int, [_vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double),
+                                        ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), _vp]),
     "rpgp_lowrank_grad_select": (_int, [_f64, _int, _f64, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_double), _vp]),
     "rpgp_lowrank_grad_prepare": (_int, [_vp, _f64, _vp, _sz, ctypes.POINTER(ctypes.c_int), _vp]),
     "rpgp_bilinear_grad_lowrank_workspace_bytes": (_sz, [_vp, _i64, _int]),

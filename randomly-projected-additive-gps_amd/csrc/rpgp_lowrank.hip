@@ -38,6 +38,11 @@
 // derivative's with its sum split at 64 (lrgx_output_kernel) and its combine with the ranks as arguments (lrgx_combine_kernel).
 // DESIGN.md 7.8.
 //
+// Panels (plans of rpgp_lowrank_create_panels): beyond the ranks the interval is cut into P equal panels instead, points of one
+// panel and of neighbouring panels interact through forms of rank <= 64 and points further apart are dropped; the rows of every
+// column are sorted by panel once per plan and the product and the derivative run kernels of their own (lrp_* / lrpg_*) over
+// the sorted blocks, per panel, and in natural order.  DESIGN.md 7.9.
+//
 // Every kernel is templated on the padded rank; dispatch_pb turns the runtime value into the template argument.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -82,6 +87,21 @@ struct LowrankPlan {
   double tol = 0.0;                      // the plan's tail tolerance
   int cap = kMaxRank;                    // largest rank the plan selects (rpgp_lowrank_create_cap: up to kCapRank)
   int ld = kMaxRank;                     // its buffers hold ld x ld coefficients: 64, or the padded cap above 64
+  // a panel plan (rpgp_lowrank_create_panels; 0 panels: the single-interval plan above).  coef / dcoef / ccoef are then C0 / D0
+  // / C0 in float64 at half-width hp, xt the LOCAL coordinates [J][N] in natural order
+  int panels = 0;
+  double hp = 0.0;                       // panel half-width h / panels
+  int nbmax = 0;                         // projection blocks reserved per column: N / 2048 + panels
+  const float *coef1 = nullptr;          // pb x pb, fp32: the neighbour form C1 (x in the lower panel, y in the upper)
+  const uint8_t *pidx = nullptr;         // [J][N] panel of every (column, row), natural order
+  const int *perm = nullptr;             // [J][nbmax 2048] rows in panel order, every (column, panel) padded to whole blocks: -1
+  const float *xs = nullptr;             // [J][nbmax 2048] local coordinates in that order (0 in a padded slot)
+  const int *bstart = nullptr;           // [J][panels + 1] first block of every panel; [panels]: the column's block count
+  const double *dcoef1 = nullptr;        // qb x qb, fp64: D1
+  const double *ccoef1 = nullptr;        // pb x pb, fp64: C1
+  double bounds[3] = {0.0, 0.0, 0.0};    // per-entry bounds of the product: tail of C0, tail of C1, largest dropped value
+  int q_sel = 0;                         // the derivative rank of the selection, and its float64 blocks (leading dimension
+  std::vector<double> hd0, hd1, hc0, hc1;  // pad8(q_sel) / pb) kept on the host for rpgp_lowrank_grad_prepare
 };
 
 // side of the coefficient blocks of a plan with the rank cap `cap`: rpgp_lowrank_create's 64 up to there, the padded cap above
@@ -1702,9 +1722,681 @@ int launch_grad_wide(const LowrankPlan &P, const float *w, const float *L, const
   });
 }
 
+// ---- panels: any half-width at the per-row work of a rank <= 64 plan (rpgp_lowrank_create_panels) -----------------------------
+// [-h, h] is cut into P equal panels of half-width hp = h / P; panel k has the centre c_k = -h + (2k + 1) hp and the local
+// coordinate x = (a - c_k) / hp.  Two points of one panel interact through C0 (the single-interval form at hp), a point of panel
+// k with one of panel k + 1 through C1, the coefficients of exp2(-hp^2 (x - y - 2)^2) (the opposite order: C1^T), and points two
+// or more panels apart, at least 2 hp apart, are dropped: exp2(-4 hp^2).  D0, D1 and -D1^T are the same for the derivative.
+// Every kernel below is new; none of the kernels above serves a panel plan.  DESIGN.md 7.9.
+constexpr int kMaxPanels = 16;           // hp <= 6.4 at p, q <= 64: half-widths up to about 100
+constexpr int kPanelLdsBytes = 32768;    // U of one column chunk in the output pass
+
+// the coefficients of cheb2d_coefficients for the shifted argument: F(hp (x - y - shift)), F(d) = exp2(-d^2), or
+// -(d / kappa) exp2(-d^2) for the derivative.  No symmetry is imposed (shift 2 has none).
+void cheb2d_shifted(double hp, double shift, bool deriv, std::vector<double> &c) {
+  const int M = kRefDegree;
+  std::vector<double> xs(M), cs((size_t)M * M), f((size_t)M * M), g((size_t)M * M);
+  for (int k = 0; k < M; ++k) xs[k] = cos(M_PI * (k + 0.5) / M);
+  for (int m = 0; m < M; ++m)
+    for (int k = 0; k < M; ++k) cs[(size_t)m * M + k] = cos(M_PI * m * (k + 0.5) / M);
+  for (int k = 0; k < M; ++k)
+    for (int l = 0; l < M; ++l) {
+      const double d = hp * (xs[k] - xs[l] - shift), e = exp2(-d * d);
+      f[(size_t)k * M + l] = deriv ? -(d / kKappa) * e : e;
+    }
+  for (int k = 0; k < M; ++k)
+    for (int n = 0; n < M; ++n) {
+      double s = 0.0;
+      for (int l = 0; l < M; ++l) s += f[(size_t)k * M + l] * cs[(size_t)n * M + l];
+      g[(size_t)k * M + n] = s;
+    }
+  c.assign((size_t)M * M, 0.0);
+  for (int m = 0; m < M; ++m) {
+    for (int k = 0; k < M; ++k) {
+      const double w = cs[(size_t)m * M + k];
+      for (int n = 0; n < M; ++n) c[(size_t)m * M + n] += w * g[(size_t)k * M + n];
+    }
+    const double wm = (m == 0 ? 1.0 : 2.0) / M;
+    for (int n = 0; n < M; ++n) c[(size_t)m * M + n] *= wm * (n == 0 ? 1.0 : 2.0) / M;
+  }
+}
+
+// select_rank's rule on given coefficients: the smallest p <= p_max whose tail (shells p ... plus the rounding allowance) is
+// <= tol, 0 when there is none or the last 8 shells are not at rounding level; tail_of: that bound for a given p
+struct Shells {
+  double s[kRefDegree], allowance;
+  bool resolved;
+  explicit Shells(const std::vector<double> &c) {
+    const int M = kRefDegree;
+    for (int q = 0; q < M; ++q) s[q] = 0.0;
+    for (int m = 0; m < M; ++m)
+      for (int n = 0; n < M; ++n) s[m > n ? m : n] += fabs(c[(size_t)m * M + n]);
+    double unresolved = 0.0;
+    for (int q = M - 8; q < M; ++q) unresolved += s[q];
+    resolved = unresolved <= 1e-11;
+    allowance = 1e-13 + unresolved;
+  }
+  double tail_of(int p) const {
+    double t = 0.0;
+    for (int q = kRefDegree - 1; q >= p; --q) t += s[q];
+    return t + allowance;
+  }
+  int rank(int p_max, double tol) const {
+    if (!resolved) return 0;
+    for (int p = 1; p <= p_max; ++p)
+      if (tail_of(p) <= tol) return p;
+    return 0;
+  }
+};
+
+struct PanelForms {
+  int P = 0, p = 0, q = 0;
+  double hp = 0.0, b[3] = {0, 0, 0}, d[3] = {0, 0, 0};
+  std::vector<double> c0, c1, d0, d1;    // kRefDegree-strided coefficients
+};
+
+// the forms of P panels at the tolerance, or false: a rank above 64, an unresolved form or a dropped value above the tolerance
+bool panel_forms(double h, double tol, int P, PanelForms &F) {
+  if (!(h > 0.0) || !isfinite(h) || P < 2 || P > kMaxPanels) return false;
+  const double hp = h / P;
+  // two or more panels apart: d >= 2 hp, where exp2(-d^2) and, from d = kappa on, (d / kappa) exp2(-d^2) fall (P = 2 drops nothing)
+  const double drop = P > 2 ? exp2(-4.0 * hp * hp) : 0.0;
+  const double ddrop = P > 2 ? (2.0 * hp < kKappa ? 1.0 : (2.0 * hp / kKappa) * exp2(-4.0 * hp * hp)) : 0.0;
+  if (drop > tol || ddrop > tol) return false;
+  cheb2d_coefficients(hp, F.d0, true);                    // (the largest rank of the four first: a count too small ends here)
+  const Shells t0(F.d0);
+  const int q0 = t0.rank(kMaxRank, tol);
+  if (!q0) return false;
+  cheb2d_coefficients(hp, F.c0);
+  cheb2d_shifted(hp, 2.0, false, F.c1);
+  cheb2d_shifted(hp, 2.0, true, F.d1);
+  const Shells s0(F.c0), s1(F.c1), t1(F.d1);
+  const int p0 = s0.rank(kMaxRank, tol), p1 = s1.rank(kMaxRank, tol), q1 = t1.rank(kMaxRank, tol);
+  if (!p0 || !p1 || !q1) return false;
+  F.P = P;
+  F.hp = hp;
+  F.p = p0 > p1 ? p0 : p1;
+  F.q = q0 > q1 ? q0 : q1;
+  F.b[0] = s0.tail_of(F.p), F.b[1] = s1.tail_of(F.p), F.b[2] = drop;
+  F.d[0] = t0.tail_of(F.q), F.d[1] = t1.tail_of(F.q), F.d[2] = ddrop;
+  return true;
+}
+
+// the smallest served panel count (panels 0), or that count alone
+bool panel_select(double h, double tol, int panels, PanelForms &F) {
+  if (panels) return panel_forms(h, tol, panels, F);
+  if (!(h > 0.0) || !isfinite(h)) return false;
+  int P = (int)ceil(h / 9.0);            // (hp >= 9 has no derivative rank <= 64 at any tolerance <= 2^-26: 61 at 7.86)
+  for (P = P < 2 ? 2 : P; P <= kMaxPanels; ++P)
+    if (panel_forms(h, tol, P, F)) return true;
+  return false;
+}
+
+inline int panel_nbmax(int64_t N, int P) { return (int)(N / kProjRows) + P; }
+
+// offsets (bytes) of the parts of a panel plan's buffer, each a multiple of 16
+struct PanelLayout {
+  size_t coef0, coef1, xl, xs, perm, bstart, pidx, total;
+  PanelLayout(int64_t N, int J, int P) {
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t S = (size_t)panel_nbmax(N, P) * kProjRows;
+    coef0 = 0;
+    coef1 = coef0 + (size_t)kMaxRank * kMaxRank * sizeof(float);
+    xl = coef1 + (size_t)kMaxRank * kMaxRank * sizeof(float);
+    xs = up(xl + (size_t)N * J * sizeof(float));
+    perm = up(xs + S * J * sizeof(float));
+    bstart = up(perm + S * J * sizeof(int));
+    pidx = up(bstart + (size_t)J * (P + 1) * sizeof(int));
+    total = up(pidx + (size_t)N * J);
+  }
+};
+
+// THE assignment of a prepared coordinate to (panel, local coordinate), for both orders: the panel is floor((a + h) / (2 hp))
+// clamped to [0, P - 1] (a = +h: the last panel; an inner edge: the upper panel; a NaN: panel 0), evaluated in float64 from the
+// float32 a, so it is a function of Z alone.  (A division, not a product with 1 / (2 hp): correctly rounded, it returns the
+// integer for a coordinate exactly on an edge.)
+__device__ __forceinline__ void panel_of(float a, double h, double hp, double inv_hp, int P, int &k, float &x) {
+  const double kk = fmin(fmax(floor(((double)a + h) / (2.0 * hp)), 0.0), (double)(P - 1));
+  k = (int)kk;
+  x = (float)(((double)a - (-h + (2.0 * kk + 1.0) * hp)) * inv_hp);
+}
+
+// plan: xl[j][n], pidx[j][n] in natural order
+__global__ __launch_bounds__(256) void lrp_coords_kernel(const float2v *__restrict__ rowdat, float *__restrict__ xl,
+                                                         uint8_t *__restrict__ pidx, long long N, int J, double h, double hp,
+                                                         double inv_hp, int P) {
+  const long long total = N * J;
+  for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < total; g += (long long)gridDim.x * 256) {
+    const int j = (int)(g / N);
+    const long long n = g - (long long)j * N;
+    int k;
+    float x;
+    panel_of(rowdat[n * J + j].x, h, hp, inv_hp, P, k, x);
+    xl[g] = x;
+    pidx[g] = (uint8_t)k;
+  }
+}
+
+// plan: the stable counting sort of one column by panel, one workgroup per column, no atomics.  Thread t owns the rows
+// [t chunk, (t + 1) chunk): it counts them by panel, the counts are prefix-summed over the threads (per panel) and over the panels
+// (whole projection blocks each), and the thread then places its rows in ascending order.  Every position is a prefix sum, so the
+// result is a function of Z alone.  Slots between a panel's last row and its last block's end keep perm = -1, x = 0.
+__global__ __launch_bounds__(256) void lrp_sort_kernel(const uint8_t *__restrict__ pidx, const float *__restrict__ xl,
+                                                       int *__restrict__ perm, float *__restrict__ xs, int *__restrict__ bstart,
+                                                       int N, int P, int nbmax) {
+  __shared__ int cnt[kMaxPanels][257];
+  __shared__ int base[kMaxPanels];
+  const int j = blockIdx.x, t = threadIdx.x;
+  const size_t S = (size_t)nbmax * kProjRows;
+  const uint8_t *pk = pidx + (size_t)j * N;
+  const int chunk = (N + 255) / 256;
+  const int i0 = t * chunk < N ? t * chunk : N, i1 = i0 + chunk < N ? i0 + chunk : N;
+  for (int k = 0; k < P; ++k) cnt[k][t] = 0;
+  for (int i = i0; i < i1; ++i) {
+    const int k = pk[i] < P ? pk[i] : P - 1;
+    cnt[k][t] += 1;
+  }
+  for (size_t s = t; s < S; s += 256) {
+    perm[j * S + s] = -1;
+    xs[j * S + s] = 0.f;
+  }
+  __syncthreads();
+  if (t < P) {
+    int run = 0;
+    for (int u = 0; u < 256; ++u) {
+      const int v = cnt[t][u];
+      cnt[t][u] = run;
+      run += v;
+    }
+    cnt[t][256] = run;
+  }
+  __syncthreads();
+  if (t == 0) {
+    int b = 0;
+    for (int k = 0; k < P; ++k) {
+      bstart[j * (P + 1) + k] = b;
+      base[k] = b * kProjRows;
+      b += (cnt[k][256] + kProjRows - 1) / kProjRows;
+    }
+    bstart[j * (P + 1) + P] = b;
+  }
+  __syncthreads();
+  for (int i = i0; i < i1; ++i) {
+    const int k = pk[i] < P ? pk[i] : P - 1;
+    const int pos = base[k] + cnt[k][t];
+    cnt[k][t] += 1;
+    perm[j * S + pos] = i;
+    xs[j * S + pos] = xl[(size_t)j * N + i];
+  }
+}
+
+// (a) lr_project_kernel's body over the sorted slots of a column: block b covers the slots [2048 b, 2048 (b + 1)), all of one
+// panel; V is read through the permutation (a padded slot: row 0, counted with v = 0).  A block past the column's count leaves.
+// The derivative's projections of L and R are this kernel too.  grid (nbmax, jn, T)
+template <int PB>
+__global__ __launch_bounds__(256) void lrp_project_kernel(const float *__restrict__ xs, const int *__restrict__ perm,
+                                                          const int *__restrict__ bstart, const float *__restrict__ V,
+                                                          double *__restrict__ part, int T, int j0, int jn, int P, int nbmax) {
+  __shared__ double red[4 * PB];
+  const int b = blockIdx.x, jj = blockIdx.y, t = blockIdx.z;
+  if (b >= bstart[(j0 + jj) * (P + 1) + P]) return;
+  const size_t s0 = ((size_t)(j0 + jj) * nbmax + b) * kProjRows + threadIdx.x;
+  float xv[kProjRowsPerThread], vv[kProjRowsPerThread];
+  int pr[kProjRowsPerThread];
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {
+    xv[u] = xs[s0 + u * 256];
+    pr[u] = perm[s0 + u * 256];
+  }
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) vv[u] = V[(size_t)(pr[u] < 0 ? 0 : pr[u]) * T + t];
+  __builtin_amdgcn_sched_barrier(0);
+  double acc[PB];
+#pragma unroll
+  for (int m = 0; m < PB; ++m) acc[m] = 0.0;
+#pragma unroll
+  for (int u = 0; u < kProjRowsPerThread; ++u) {
+    const double xi = (double)xv[u], v = pr[u] < 0 ? 0.0 : (double)vv[u], x2 = 2.0 * xi;
+    double tm2 = 1.0, tm1 = xi;
+    acc[0] += v;
+    acc[1] = __builtin_fma(xi, v, acc[1]);
+#pragma unroll
+    for (int m = 2; m < PB; ++m) {
+      const double tm = __builtin_fma(x2, tm1, -tm2);     // T_m = 2x T_{m-1} - T_{m-2}
+      acc[m] = __builtin_fma(tm, v, acc[m]);
+      tm2 = tm1;
+      tm1 = tm;
+    }
+  }
+  constexpr int QB = PB / 4;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < PB / 2; ++i) acc[i] = swap_add<32>(acc[i], acc[i + PB / 2]);
+#pragma unroll
+  for (int i = 0; i < QB; ++i) {
+    double s = swap_add<16>(acc[i], acc[i + QB]);
+    s += dpp_d<0xb1>(s);    // quad_perm [1,0,3,2]
+    s += dpp_d<0x4e>(s);    // quad_perm [2,3,0,1]
+    s += dpp_d<0x141>(s);   // row_half_mirror
+    s += dpp_d<0x140>(s);   // row_mirror
+    if ((lane & 15) == i) red[w * PB + QB * (lane >> 4) + i] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < PB) {
+    const int m = threadIdx.x;
+    part[(((size_t)b * jn + jj) * T + t) * PB + m] = (red[m] + red[PB + m]) + (red[2 * PB + m] + red[3 * PB + m]);
+  }
+}
+
+// W of the panels k - 1, k, k + 1 of (projection jj, t) into ws[3][pb]: thread (which, n) adds that panel's blocks in ascending
+// order; a panel outside [0, P) is zero
+__device__ __forceinline__ void panel_sums(const double *__restrict__ part, const int *__restrict__ bs, double *ws, int k, int P,
+                                           int jn, int jj, int T, int t, int pb) {
+  for (int e = threadIdx.x; e < 3 * pb; e += 256) {
+    const int which = e / pb, n = e - which * pb, kk = k - 1 + which;
+    double s = 0.0;
+    if (kk >= 0 && kk < P)
+      for (int b = bs[kk]; b < bs[kk + 1]; ++b) s += part[(((size_t)b * jn + jj) * T + t) * pb + n];
+    ws[e] = s;
+  }
+}
+
+// (b) U[jj][t][k][m] = (scale w_j) (C0 W_k + C1 W_{k+1} + C1^T W_{k-1})[m] in float64, the three products in that order, each
+// over n ascending.  `w`: the weight of projection j0, or null; null and a weight of 1 give the same bits (scale * 1.0 is scale).
+// grid (jn P, T)
+template <int PB>
+__global__ __launch_bounds__(256) void lrp_combine_kernel(const double *__restrict__ part, const float *__restrict__ coef0,
+                                                          const float *__restrict__ coef1, const float *__restrict__ w,
+                                                          const int *__restrict__ bstart, float *__restrict__ U, int T, int j0,
+                                                          int jn, int P, float scale) {
+  __shared__ double ws[3 * PB];
+  const int jj = blockIdx.x / P, k = blockIdx.x - jj * P, t = blockIdx.y;
+  panel_sums(part, bstart + (j0 + jj) * (P + 1), ws, k, P, jn, jj, T, t, PB);
+  __syncthreads();
+  const int m = threadIdx.x;
+  if (m >= PB) return;
+  const double sj = w ? (double)scale * (double)w[jj] : (double)scale;
+  double a = 0.0;
+  for (int n = 0; n < PB; ++n) a = __builtin_fma((double)coef0[m * PB + n], ws[PB + n], a);
+  for (int n = 0; n < PB; ++n) a = __builtin_fma((double)coef1[m * PB + n], ws[2 * PB + n], a);
+  for (int n = 0; n < PB; ++n) a = __builtin_fma((double)coef1[n * PB + m], ws[n], a);
+  U[(((size_t)jj * T + t) * P + k) * PB + m] = (float)(sj * a);
+}
+
+// (c) lr_output_kernel in natural row order, each lane on its own panel's U.  LDS holds U[.][t] of a chunk of jc projections,
+// P rows of PB + 1 floats each: lanes of a wave read the same m of different panels' rows, and the odd stride puts those rows
+// PB + 1 banks apart (lanes of one panel read one address, a broadcast) where a stride of PB, a multiple of 8, would send every
+// panel to the same few banks.  jc = 32 KB / (P (PB + 1) 4 B): 31 projections at P = 4, PB = 64, 7 at P = 16; 32 KB per
+// workgroup leaves five workgroups (20 waves) per CU.  Wave g takes the projections jj = g (mod 4) of every chunk in ascending
+// order, so the order of the additions does not depend on the chunking.  grid (row blocks of 64, T), dynamic LDS
+template <int PB>
+__global__ __launch_bounds__(256) void lrp_output_kernel(const float *__restrict__ xl, const uint8_t *__restrict__ pidx,
+                                                         const float *__restrict__ U, const float *__restrict__ V,
+                                                         float *__restrict__ out, int N, int T, int j0, int jn, int r0, int r1,
+                                                         float noise, int P, int jc) {
+  extern __shared__ float su[];
+  __shared__ float sacc[4][kOutRows];
+  constexpr int LD = PB + 1;
+  const int t = blockIdx.y;
+  const int r = threadIdx.x & (kOutRows - 1), g = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
+  const int i = blockIdx.x * kOutRows + r;
+  const bool mine = i >= r0 && i < r1;
+  int ic = i > r0 ? i : r0;
+  ic = ic < r1 ? ic : r1 - 1;
+  ic = ic < N ? ic : N - 1;
+  ic = ic > 0 ? ic : 0;
+  float vn = 0.f;
+  if (g == 0 && noise != 0.f) vn = V[(size_t)(i < N ? i : N - 1) * T + t];
+  float acc = 0.f;
+  for (int c0 = 0; c0 < jn; c0 += jc) {
+    const int cn = jn - c0 < jc ? jn - c0 : jc;
+    if (c0) __syncthreads();                              // (the previous chunk's readers are done)
+    for (int e = threadIdx.x; e < cn * P * PB; e += 256) {
+      const int c = e / (P * PB), rem = e - c * (P * PB), row = rem / PB, m = rem - row * PB;
+      su[(c * P + row) * LD + m] = U[((size_t)(c0 + c) * T + t) * P * PB + rem];
+    }
+    __syncthreads();
+    for (int jj = c0 + ((g - c0) & 3); jj < c0 + cn; jj += 4) {
+      const size_t o = (size_t)(j0 + jj) * N + ic;
+      const float x = xl[o], x2 = 2.f * x;
+      int pk = pidx[o];
+      pk = pk < P ? pk : P - 1;
+      const float *u = su + ((jj - c0) * P + pk) * LD;
+      float b1 = 0.f, b2 = 0.f;                           // Clenshaw: b_k = U_k + 2x b_{k+1} - b_{k+2}
+#pragma unroll
+      for (int k = PB - 1; k >= 1; --k) {
+        const float bk = __builtin_fmaf(x2, b1, u[k] - b2);
+        b2 = b1;
+        b1 = bk;
+      }
+      acc += __builtin_fmaf(x, b1, u[0] - b2);
+    }
+  }
+  sacc[g][r] = acc;
+  __syncthreads();
+  if (g != 0 || i >= N) return;
+  float res = mine ? (sacc[0][r] + sacc[1][r]) + (sacc[2][r] + sacc[3][r]) : 0.f;
+  if (noise != 0.f) res = __builtin_fmaf(noise, vn, res);
+  out[(size_t)i * T + t] = res;
+}
+
+inline int panel_chunk(const LowrankPlan &P, int jn) {
+  const int jc = kPanelLdsBytes / (P.panels * (P.pb + 1) * (int)sizeof(float));
+  return jc < 1 ? 1 : (jc < jn ? jc : jn);
+}
+
+// workspace of the product of a panel plan: part (nbmax x jn x T x PB doubles), U (jn x T x P x PB floats)
+inline size_t panel_ws_bytes(const LowrankPlan &P, int jn, int T) {
+  return (size_t)jn * T * P.pb * ((size_t)P.nbmax * sizeof(double) + (size_t)P.panels * sizeof(float));
+}
+
+// w: the weights (all of them; the launches offset by j0) or null
+int launch_panels(const LowrankPlan &P, const float *w, const float *V, float *out, int N, int T, int j0, int jn, int r0,
+                  int r1, float scale, float noise, void *ws, hipStream_t st) {
+  double *part = reinterpret_cast<double *>(ws);
+  float *U = reinterpret_cast<float *>(part + (size_t)P.nbmax * jn * T * P.pb);
+  const int jc = panel_chunk(P, jn);
+  const size_t lds = (size_t)jc * P.panels * (P.pb + 1) * sizeof(float);
+  return dispatch_pb<kMaxRank>(P.pb, [&](auto pbc) {
+    constexpr int PB = decltype(pbc)::value;
+    hipLaunchKernelGGL(lrp_project_kernel<PB>, dim3(P.nbmax, jn, T), dim3(256), 0, st, P.xs, P.perm, P.bstart, V, part, T, j0,
+                       jn, P.panels, P.nbmax);
+    hipLaunchKernelGGL(lrp_combine_kernel<PB>, dim3(jn * P.panels, T), dim3(256), 0, st, part, P.coef, P.coef1,
+                       w ? w + j0 : nullptr, P.bstart, U, T, j0, jn, P.panels, scale);
+    hipLaunchKernelGGL(lrp_output_kernel<PB>, dim3((N + kOutRows - 1) / kOutRows, T), dim3(256), lds, st, P.xt, P.pidx, U, V,
+                       out, N, T, j0, jn, r0, r1, noise, P.panels, jc);
+    return (int)hipGetLastError();
+  });
+}
+
+// (b) of the derivative, per (projection, panel, t), in float64, with the padded ranks as arguments (a latency chain of one
+// workgroup, as lrgx_combine_kernel):
+//   U[jj][k][t][0][m] = (scale w_j) (D0 W^R_k + D1 W^R_{k+1} - D1^T W^R_{k-1})[m],  [1][m]: the same of W^L
+//   gsp[jj][k][t]     = W^L_k^T (C0 W^R_k + C1 W^R_{k+1} + C1^T W^R_{k-1})   (unweighted; leading dimension pc)
+// grid (jn P, T)
+__global__ __launch_bounds__(256) void lrpg_combine_kernel(const double *__restrict__ partL, const double *__restrict__ partR,
+                                                           const double *__restrict__ d0, const double *__restrict__ d1,
+                                                           const double *__restrict__ c0, const double *__restrict__ c1,
+                                                           const float *__restrict__ wt, const int *__restrict__ bstart,
+                                                           double *__restrict__ U, double *__restrict__ gsp, int T, int j0,
+                                                           int jn, int P, int p, int pc, int pb, int qb, double scale) {
+  __shared__ double wl[3 * kMaxRank], wr[3 * kMaxRank], cw[kMaxRank];
+  const int jj = blockIdx.x / P, k = blockIdx.x - jj * P, t = blockIdx.y;
+  const int *bs = bstart + (j0 + jj) * (P + 1);
+  panel_sums(partL, bs, wl, k, P, jn, jj, T, t, pb);
+  panel_sums(partR, bs, wr, k, P, jn, jj, T, t, pb);
+  __syncthreads();
+  const double sj = wt ? scale * (double)wt[jj] : scale;
+  const int m = threadIdx.x;
+  if (m < qb) {
+    double ur = 0.0, ul = 0.0;
+    for (int n = 0; n < qb; ++n) {
+      const double d = d0[m * qb + n];
+      ur = __builtin_fma(d, wr[pb + n], ur);
+      ul = __builtin_fma(d, wl[pb + n], ul);
+    }
+    for (int n = 0; n < qb; ++n) {
+      const double d = d1[m * qb + n];
+      ur = __builtin_fma(d, wr[2 * pb + n], ur);
+      ul = __builtin_fma(d, wl[2 * pb + n], ul);
+    }
+    for (int n = 0; n < qb; ++n) {
+      const double d = -d1[n * qb + m];
+      ur = __builtin_fma(d, wr[n], ur);
+      ul = __builtin_fma(d, wl[n], ul);
+    }
+    double *u = U + (((size_t)jj * P + k) * T + t) * 2 * qb;
+    u[m] = sj * ur;
+    u[qb + m] = sj * ul;
+  }
+  if (m < pb) {
+    double s = 0.0;
+    if (m < p) {
+      for (int n = 0; n < p; ++n) s = __builtin_fma(c0[m * pc + n], wr[pb + n], s);
+      for (int n = 0; n < p; ++n) s = __builtin_fma(c1[m * pc + n], wr[2 * pb + n], s);
+      for (int n = 0; n < p; ++n) s = __builtin_fma(c1[n * pc + m], wr[n], s);
+    }
+    cw[m] = s;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int n = 0; n < p; ++n) s = __builtin_fma(wl[pb + n], cw[n], s);
+    gsp[((size_t)jj * P + k) * T + t] = s;
+  }
+}
+
+// (c) of the derivative: lrg_output_kernel with each lane on its own panel's U (read from global memory: P T 2 QB doubles per
+// projection do not fit LDS).  Workgroup 0 sums gsp in a fixed order: per component (comp: gout = gcomp, thread jj adds panels,
+// then t, ascending) or all of it (gout = gscale: jj, panel, t ascending).  grid (row blocks of 64)
+template <int QB>
+__global__ __launch_bounds__(256) void lrpg_output_kernel(const float *__restrict__ xl, const uint8_t *__restrict__ pidx,
+                                                          const double *__restrict__ U, const double *__restrict__ gsp,
+                                                          const float *__restrict__ L, const float *__restrict__ R,
+                                                          float *__restrict__ gZ, float *__restrict__ gout, int N, int T, int j0,
+                                                          int jn, int ldg, int P, int comp) {
+  __shared__ float sres[kOutRows][kPrepMaxJ + 1];
+  const int r = threadIdx.x & (kOutRows - 1);
+  const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kOutRows);
+  const int row0 = blockIdx.x * kOutRows;
+  const int i = row0 + r;
+  const bool ok = i < N;
+  const int ic = ok ? i : N - 1;
+  for (int jj = wv; jj < jn; jj += 4) {
+    const size_t o = (size_t)(j0 + jj) * N + ic;
+    int pk = pidx[o];
+    pk = pk < P ? pk : P - 1;
+    const double *u = U + ((size_t)jj * P + pk) * T * 2 * QB;
+    double q[QB];
+#pragma unroll
+    for (int m = 0; m < QB; ++m) q[m] = 0.0;
+    for (int t = 0; t < T; ++t) {
+      const double l = ok ? (double)L[(size_t)i * T + t] : 0.0;
+      const double rr = ok ? (double)R[(size_t)i * T + t] : 0.0;
+      const double *ut = u + (size_t)t * 2 * QB;
+#pragma unroll
+      for (int m = 0; m < QB; ++m) q[m] = __builtin_fma(l, ut[m], __builtin_fma(rr, ut[QB + m], q[m]));
+    }
+    const double x = (double)xl[o], x2 = 2.0 * x;
+    double b1 = 0.0, b2 = 0.0;
+#pragma unroll
+    for (int k = QB - 1; k >= 1; --k) {
+      const double bk = __builtin_fma(x2, b1, q[k] - b2);
+      b2 = b1;
+      b1 = bk;
+    }
+    sres[r][jj] = (float)__builtin_fma(x, b1, q[0] - b2);
+  }
+  __syncthreads();
+  const int rows = N - row0 < kOutRows ? N - row0 : kOutRows;
+  for (int e = threadIdx.x; e < rows * jn; e += 256) {
+    const int rr = e / jn, c = e - rr * jn;
+    gZ[(size_t)(row0 + rr) * ldg + j0 + c] = sres[rr][c];
+  }
+  if (blockIdx.x != 0) return;
+  if (comp) {
+    if ((int)threadIdx.x < jn) {
+      double s = 0.0;
+      for (int k = 0; k < P * T; ++k) s += gsp[(size_t)threadIdx.x * P * T + k];
+      gout[j0 + threadIdx.x] = (float)s;
+    }
+  } else if (threadIdx.x == 0) {
+    double s = 0.0;
+    for (int k = 0; k < jn * P * T; ++k) s += gsp[k];
+    *gout = (float)s;
+  }
+}
+
+// workspace of the derivative of a panel plan: partL, partR (nbmax x jn x T x PB doubles each), U (jn x P x T x 2 x QB doubles),
+// gsp (jn x P x T)
+inline size_t panel_grad_ws_bytes(const LowrankPlan &P, int jn, int T) {
+  return ((size_t)P.nbmax * jn * T * grad_pb(P) * 2 + (size_t)jn * P.panels * T * (2 * P.qb + 1)) * sizeof(double);
+}
+
+// w: the weights (gout = gcomp) or null (gout = gscale)
+int launch_panels_grad(const LowrankPlan &P, const float *w, const float *L, const float *R, float *gZ, float *gout, int N,
+                       int ldg, int T, int j0, int jn, float scale, void *ws, hipStream_t st) {
+  const int pb = grad_pb(P), qb = P.qb;
+  const size_t np = (size_t)P.nbmax * jn * T * pb;
+  double *partL = reinterpret_cast<double *>(ws), *partR = partL + np;
+  double *U = partR + np, *gsp = U + (size_t)jn * P.panels * T * 2 * qb;
+  int rc = dispatch_pb<kMaxRank>(pb, [&](auto pbc) {
+    constexpr int PB = decltype(pbc)::value;
+    hipLaunchKernelGGL(lrp_project_kernel<PB>, dim3(P.nbmax, jn, T), dim3(256), 0, st, P.xs, P.perm, P.bstart, L, partL, T, j0,
+                       jn, P.panels, P.nbmax);
+    hipLaunchKernelGGL(lrp_project_kernel<PB>, dim3(P.nbmax, jn, T), dim3(256), 0, st, P.xs, P.perm, P.bstart, R, partR, T, j0,
+                       jn, P.panels, P.nbmax);
+    return (int)hipGetLastError();
+  });
+  if (rc) return rc;
+  hipLaunchKernelGGL(lrpg_combine_kernel, dim3(jn * P.panels, T), dim3(256), 0, st, partL, partR, P.dcoef, P.dcoef1, P.ccoef,
+                     P.ccoef1, w ? w + j0 : nullptr, P.bstart, U, gsp, T, j0, jn, P.panels, P.p, P.pb, pb, qb, (double)scale);
+  rc = (int)hipGetLastError();
+  if (rc) return rc;
+  return dispatch_pb<kMaxRank>(qb, [&](auto qbc) {
+    constexpr int QB = decltype(qbc)::value;
+    hipLaunchKernelGGL(lrpg_output_kernel<QB>, dim3((N + kOutRows - 1) / kOutRows), dim3(256), 0, st, P.xt, P.pidx, U, gsp, L, R,
+                       gZ, gout, N, T, j0, jn, ldg, P.panels, w ? 1 : 0);
+    return (int)hipGetLastError();
+  });
+}
+
+// rpgp_lowrank_grad_prepare of a panel plan: [D0][D1][C0][C1], 64 x 64 doubles each, from the blocks the plan's selection
+// kept on the host.  The derivative was selected with the plan, at the plan's tolerance: a smaller `tol` is not served.
+int panel_grad_prepare(LowrankPlan &P, double tol, void *dcoef, int *q_host, hipStream_t st) {
+  if ((tol < kTailTol ? tol : kTailTol) < P.tol || !P.q_sel) return 0;
+  double *dd = reinterpret_cast<double *>(dcoef);
+  const size_t blk = (size_t)kMaxRank * kMaxRank;
+  const std::vector<double> *src[4] = {&P.hd0, &P.hd1, &P.hc0, &P.hc1};
+  for (int k = 0; k < 4; ++k) {
+    hipError_t e = hipMemcpyAsync(dd + k * blk, src[k]->data(), src[k]->size() * sizeof(double), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipError_t e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  P.q = P.q_sel;
+  P.qb = pad8(P.q);
+  P.dcoef = dd;
+  P.dcoef1 = dd + blk;
+  P.ccoef = dd + 2 * blk;
+  P.ccoef1 = dd + 3 * blk;
+  *q_host = P.q;
+  return 0;
+}
+
+int create_panel_plan(const void *prep, int64_t N, int J, float max_abs, double tol, int panels, void *plan, size_t plan_bytes,
+                      int *panels_host, int *p_host, void **handle_host, hipStream_t st) {
+  *panels_host = *p_host = 0;
+  *handle_host = nullptr;
+  const double h = (double)max_abs * (1.0 + 1.0 / (1 << 20));     // (create_plan's allowance for the rounding at the ends)
+  PanelForms F;
+  if (!panel_select(h, tol, panels, F)) return 0;         // not served
+  const PanelLayout lay(N, J, F.P);
+  if (plan_bytes < lay.total) return RPGP_EWORKSPACE;
+  LowrankPlan *P = new (std::nothrow) LowrankPlan{};
+  if (!P) return RPGP_EINVAL;
+  const int pb = pad8(F.p), qb = pad8(F.q);
+  char *base = reinterpret_cast<char *>(plan);
+  P->p = F.p, P->pb = pb, P->N = N, P->J = J, P->h = h, P->tail = F.b[0] > F.b[1] ? F.b[0] : F.b[1];
+  P->tol = tol;
+  P->panels = F.P, P->hp = F.hp, P->nbmax = panel_nbmax(N, F.P);
+  for (int k = 0; k < 3; ++k) P->bounds[k] = F.b[k];
+  float *coef0 = reinterpret_cast<float *>(base + lay.coef0), *coef1 = reinterpret_cast<float *>(base + lay.coef1);
+  float *xl = reinterpret_cast<float *>(base + lay.xl), *xs = reinterpret_cast<float *>(base + lay.xs);
+  int *perm = reinterpret_cast<int *>(base + lay.perm), *bstart = reinterpret_cast<int *>(base + lay.bstart);
+  uint8_t *pidx = reinterpret_cast<uint8_t *>(base + lay.pidx);
+  P->coef = coef0, P->coef1 = coef1, P->xt = xl, P->xs = xs, P->perm = perm, P->bstart = bstart, P->pidx = pidx;
+  std::vector<float> cf0((size_t)pb * pb, 0.f), cf1((size_t)pb * pb, 0.f);
+  copy_leading_block(F.c0, F.p, cf0.data(), pb);
+  copy_leading_block(F.c1, F.p, cf1.data(), pb);
+  P->q_sel = F.q;
+  P->hd0.assign((size_t)qb * qb, 0.0), P->hd1.assign((size_t)qb * qb, 0.0);
+  P->hc0.assign((size_t)pb * pb, 0.0), P->hc1.assign((size_t)pb * pb, 0.0);
+  copy_leading_block(F.d0, F.q, P->hd0.data(), qb);
+  copy_leading_block(F.d1, F.q, P->hd1.data(), qb);
+  copy_leading_block(F.c0, F.p, P->hc0.data(), pb);
+  copy_leading_block(F.c1, F.p, P->hc1.data(), pb);
+  int rc = (int)hipMemcpyAsync(coef0, cf0.data(), cf0.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (!rc) rc = (int)hipMemcpyAsync(coef1, cf1.data(), cf1.size() * sizeof(float), hipMemcpyHostToDevice, st);
+  if (!rc) {
+    const long long total = N * J;
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const float2v *rowdat = reinterpret_cast<const float2v *>(reinterpret_cast<const float *>(prep) + kPrepRowdatOffsetFloats);
+    hipLaunchKernelGGL(lrp_coords_kernel, dim3(blocks), dim3(256), 0, st, rowdat, xl, pidx, (long long)N, J, h, F.hp, 1.0 / F.hp,
+                       F.P);
+    hipLaunchKernelGGL(lrp_sort_kernel, dim3(J), dim3(256), 0, st, pidx, xl, perm, xs, bstart, (int)N, F.P, P->nbmax);
+    rc = (int)hipGetLastError();
+  }
+  if (!rc) rc = (int)hipStreamSynchronize(st);            // (the host copies of the coefficients go out of scope)
+  if (rc) {
+    delete P;
+    return rc;
+  }
+  *panels_host = F.P;
+  *p_host = F.p;
+  *handle_host = P;
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int rpgp_lowrank_panels_select(double h, double tol, int panels, int *panels_host, double *hp_host, int *p_host, int *q_host,
+                               double *bounds_host, double *dbounds_host, double *coef_host) {
+  if (!panels_host || !(tol > 0.0) || panels < 0 || panels == 1 || panels > kMaxPanels) return RPGP_EINVAL;
+  *panels_host = 0;
+  PanelForms F;
+  if (!panel_select(h, tol < kTailTol ? tol : kTailTol, panels, F)) return 0;
+  *panels_host = F.P;
+  if (hp_host) *hp_host = F.hp;
+  if (p_host) *p_host = F.p;
+  if (q_host) *q_host = F.q;
+  for (int k = 0; k < 3; ++k) {
+    if (bounds_host) bounds_host[k] = F.b[k];
+    if (dbounds_host) dbounds_host[k] = F.d[k];
+  }
+  if (coef_host) {                                        // [C0][C1][D0][D1], 64 x 64 doubles each, zero outside p x p / q x q
+    const size_t blk = (size_t)kMaxRank * kMaxRank;
+    for (size_t e = 0; e < 4 * blk; ++e) coef_host[e] = 0.0;
+    copy_leading_block(F.c0, F.p, coef_host, kMaxRank);
+    copy_leading_block(F.c1, F.p, coef_host + blk, kMaxRank);
+    copy_leading_block(F.d0, F.q, coef_host + 2 * blk, kMaxRank);
+    copy_leading_block(F.d1, F.q, coef_host + 3 * blk, kMaxRank);
+  }
+  return 0;
+}
+
+int rpgp_lowrank_panels_max(void) { return kMaxPanels; }
+
+size_t rpgp_lowrank_panels_plan_bytes(int64_t N, int J) {
+  if (N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ) return 0;
+  return PanelLayout(N, J, kMaxPanels).total;
+}
+
+int rpgp_lowrank_create_panels(const void *prep, int64_t N, int J, float max_abs, double tol, int panels, void *plan,
+                               size_t plan_bytes, int *panels_host, int *p_host, void **handle_host, void *stream) {
+  if (!prep || !plan || !panels_host || !p_host || !handle_host || N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ)
+    return RPGP_EINVAL;
+  if (!(tol > 0.0) || panels < 0 || panels == 1 || panels > kMaxPanels) return RPGP_EINVAL;
+  // (the sorted slots of a column are indexed by int: N / 2048 + 16 blocks of 2048 stay below 2^31 for every N up to 2^31 - 2^16)
+  if (N > 0x7fffffffLL - 65536) return RPGP_EINVAL;
+  return create_panel_plan(prep, N, J, max_abs, tol < kTailTol ? tol : kTailTol, panels, plan, plan_bytes, panels_host, p_host,
+                           handle_host, reinterpret_cast<hipStream_t>(stream));
+}
+
+int rpgp_lowrank_panels_info(const void *handle, int *panels_host, double *hp_host, int *p_host, int *q_host,
+                             double *bounds_host) {
+  const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
+  if (!P) return RPGP_EINVAL;
+  if (panels_host) *panels_host = P->panels;
+  if (hp_host) *hp_host = P->panels ? P->hp : P->h;
+  if (p_host) *p_host = P->p;
+  if (q_host) *q_host = P->panels ? P->q_sel : P->q;
+  if (bounds_host)
+    for (int k = 0; k < 3; ++k) bounds_host[k] = P->bounds[k];
+  return 0;
+}
 
 int rpgp_lowrank_select(double h, int p_max, int *p_host, double *tail_host, double *coef_host) {
   return select_to_host(h, p_max, kTailTol, false, p_host, tail_host, coef_host);
@@ -1727,6 +2419,7 @@ int rpgp_lowrank_create_cap(const void *prep, int64_t N, int J, float max_abs, d
 size_t rpgp_lowrank_grad_bytes(const void *handle) {
   const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
   if (!P) return 0;
+  if (P->panels) return (size_t)4 * kMaxRank * kMaxRank * sizeof(double);      // D0, D1, C0, C1
   return (size_t)2 * P->ld * P->ld * sizeof(double);      // D and C (64: RPGP_LOWRANK_GRAD_BYTES)
 }
 
@@ -1749,6 +2442,7 @@ int rpgp_lowrank_destroy(void *handle) {
 size_t rpgp_mvm_sym_lowrank_workspace_bytes(const void *handle, int64_t N, int T) {
   const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
   if (!P || N <= 0 || N > 0x7fffffffLL || T <= 0) return 0;
+  if (P->panels) return panel_ws_bytes(*P, P->J, T);
   return (size_t)P->J * T * P->pb * ((size_t)proj_blocks(N) * sizeof(double) + sizeof(float));
 }
 
@@ -1766,6 +2460,15 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
   const int n = (int)N, jn = j1 - j0;
   // a rank of a pair-sharded call writes its row slice of K v (and the noise term, if it was given one, on every row)
   const int r0 = (int)((int64_t)n * rank / world), r1 = (int)((int64_t)n * (rank + 1) / world);
+  if (P->panels) {
+    const bool prof = rpgp_internal::prof_open(st);
+    int rc = launch_panels(*P, nullptr, V, out, n, T, j0, jn, r0, r1, scale, noise, workspace, st);
+    if (prof) {
+      const int pc = rpgp_internal::prof_close(st);
+      if (!rc) rc = pc;
+    }
+    return rc;
+  }
   double *part = reinterpret_cast<double *>(workspace);
   float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
   const bool prof = rpgp_internal::prof_open(st);
@@ -1794,6 +2497,7 @@ int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoe
   *q_host = 0;
   P->q = P->qb = 0;
   P->dcoef = nullptr;
+  if (P->panels) return panel_grad_prepare(*P, tol, dcoef, q_host, reinterpret_cast<hipStream_t>(stream));
   std::vector<double> c;
   double tail = 0.0;
   const int q = select_rank(P->h, P->cap, tol < kTailTol ? tol : kTailTol, &tail, c, true);
@@ -1825,6 +2529,7 @@ int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoe
 size_t rpgp_bilinear_grad_lowrank_workspace_bytes(const void *handle, int64_t N, int T) {
   const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
   if (!P || !P->q || N <= 0 || N > 0x7fffffffLL || T <= 0) return 0;
+  if (P->panels) return panel_grad_ws_bytes(*P, P->J, T);
   return grad_ws_bytes(*P, N, P->J, T);
 }
 
@@ -1835,6 +2540,11 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
   if (!P || !L || !R || !gZ || !gscale || N <= 0 || T <= 0 || T > 65535) return RPGP_EINVAL;
   if (N != P->N || j0 < 0 || j1 <= j0 || j1 > P->J || ldg < P->J) return RPGP_EINVAL;
   if (!P->q) return RPGP_EINVAL;                          // no derivative rank: the caller runs rpgp_bilinear_grad
+  if (P->panels) {
+    if (!workspace || workspace_bytes < panel_grad_ws_bytes(*P, j1 - j0, T)) return RPGP_EWORKSPACE;
+    return launch_panels_grad(*P, nullptr, L, R, gZ, gscale, (int)N, ldg, T, j0, j1 - j0, scale, workspace,
+                              reinterpret_cast<hipStream_t>(stream));
+  }
   if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int n = (int)N, jn = j1 - j0;
@@ -1863,6 +2573,15 @@ int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const fl
   if (!workspace || workspace_bytes < need) return RPGP_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int n = (int)N, jn = j1 - j0;
+  if (P->panels) {
+    const bool prof = rpgp_internal::prof_open(st);
+    int rc = launch_panels(*P, weights, V, out, n, T, j0, jn, 0, n, scale, noise, workspace, st);
+    if (prof) {
+      const int pc = rpgp_internal::prof_close(st);
+      if (!rc) rc = pc;
+    }
+    return rc;
+  }
   double *part = reinterpret_cast<double *>(workspace);
   float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
   const bool prof = rpgp_internal::prof_open(st);
@@ -1887,6 +2606,11 @@ int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights
   if (!P || !weights || !L || !R || !gZ || !gcomp || N <= 0 || T <= 0 || T > 65535) return RPGP_EINVAL;
   if (N != P->N || J != P->J || j0 < 0 || j1 <= j0 || j1 > J) return RPGP_EINVAL;
   if (!P->q) return RPGP_EINVAL;                          // no derivative rank: the caller runs rpgp_family_bilinear_grad
+  if (P->panels) {
+    if (!workspace || workspace_bytes < panel_grad_ws_bytes(*P, j1 - j0, T)) return RPGP_EWORKSPACE;
+    return launch_panels_grad(*P, weights, L, R, gZ, gcomp, (int)N, P->J, T, j0, j1 - j0, scale, workspace,
+                              reinterpret_cast<hipStream_t>(stream));
+  }
   if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int n = (int)N, jn = j1 - j0;

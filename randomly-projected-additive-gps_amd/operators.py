@@ -13,6 +13,20 @@ from .hostvals import host_float
 from . import settings
 
 
+def _panels_keyword(plan_fn):
+    """{"panels": True} for a backend's lowrank_train_plan under settings.lowrank_panels, {} with the setting off (the call is
+    then today's) or for a backend whose plan function does not take the keyword: no panels."""
+    if not settings.lowrank_panels.on():
+        return {}
+    import inspect
+    try:
+        params = inspect.signature(plan_fn).parameters
+    except (TypeError, ValueError):
+        return {}
+    takes = "panels" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
+    return {"panels": True} if takes else {}
+
+
 class LinearOperator:
     """Minimal protocol base."""
 
@@ -200,7 +214,8 @@ class AdditiveRPOperator(LinearOperator):
                 if self._prep is None:
                     self._prep = prepare(self.Z1.detach())
                 cap = settings.lowrank_max_rank.value()     # (passed on only above the default: 64 is the plan's own)
-                plan = plan_fn(self._prep, self._scale, float(noise), **({"max_rank": cap} if cap > 64 else {}))
+                plan = plan_fn(self._prep, self._scale, float(noise), **({"max_rank": cap} if cap > 64 else {}),
+                               **_panels_keyword(plan_fn))
                 if plan is not None:
                     self._lowrank = plan
         return self._lowrank or None
@@ -238,6 +253,13 @@ class AdditiveRPOperator(LinearOperator):
         """(p, q) of the low-rank form that serves this operator, or None."""
         lr = getattr(self, "_lowrank", None)
         return (lr.p, lr.q) if lr else None
+
+    @property
+    def lowrank_panels(self):
+        """Panel count P >= 2 of the panel plan that serves this operator (settings.lowrank_panels), 0 for a single-interval
+        plan, None when the low-rank form does not serve it."""
+        lr = getattr(self, "_lowrank", None)
+        return int(getattr(lr, "panels", 0)) if lr else None
 
     def native_descriptor(self, noise=0.0):
         """`struct rpgp_operator` for the native mBCG executor, or None when the operator must stay on the Python path
@@ -851,10 +873,11 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
                 if self._prep is None:
                     self._prep = prepare(self.Z1.detach())
                 cap = settings.lowrank_max_rank.value()     # (passed on only above the default: 64 is the plan's own)
-                if self._prep.fast_ok or cap > 64:          # (above 64 the plan decides: a finite range, not the sweep's guard)
+                pk = _panels_keyword(plan_fn)
+                if self._prep.fast_ok or cap > 64 or pk:    # (above 64 the plan decides: a finite range, not the sweep's guard)
                     wabs = float(self.fam.weights.abs().sum())
                     plan = plan_fn(self._prep, self._scale, float(noise), mass=self._scale * wabs,
-                                   **({"max_rank": cap} if cap > 64 else {}))
+                                   **({"max_rank": cap} if cap > 64 else {}), **pk)
                     if plan is not None:
                         self._lowrank = plan
         return self._lowrank or None

@@ -283,16 +283,36 @@ def lowrank_grad_select(h, q_max=64, tol=_LOWRANK_TAIL):
 LOWRANK_KERNEL_RANK = 128       # largest rank cap of a LowrankTrainPlan (rpgp_lowrank_create_cap)
 
 
+def lowrank_panels_select(h, tol=_LOWRANK_TAIL, panels=0):
+    """The panel forms of rpgp_lowrank_panels_select (host only) for the half-width h: None when no panel count (panels = 0:
+    the smallest of 2 ... 16; else that count alone) has all four ranks <= 64 and all six bounds within min(tol, 2^-26), else a
+    dict with P, h_p, p, q, `bounds` / `dbounds` (tail of the same-panel form, tail of the neighbour form, largest dropped value,
+    of the product / the derivative) and the float64 blocks C0, C1 (p x p), D0, D1 (q x q)."""
+    import ctypes
+    import numpy as np
+    lib = _lib.load()
+    P, p, q, hp = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0.0)
+    b, d, c = np.zeros(3), np.zeros(3), np.zeros((4, 64, 64))
+    _lib.check(lib.rpgp_lowrank_panels_select(float(h), float(tol), int(panels), ctypes.byref(P), ctypes.byref(hp),
+                                              ctypes.byref(p), ctypes.byref(q), b.ctypes.data, d.ctypes.data, c.ctypes.data),
+               "rpgp_lowrank_panels_select")
+    if not P.value:
+        return None
+    p, q = int(p.value), int(q.value)
+    return {"P": int(P.value), "h_p": float(hp.value), "p": p, "q": q, "bounds": b, "dbounds": d,
+            "C0": c[0, :p, :p].copy(), "C1": c[1, :p, :p].copy(), "D0": c[2, :q, :q].copy(), "D1": c[3, :q, :q].copy()}
+
+
 class LowrankTrainPlan:
     """Training plan of one Prepared (rpgp_lowrank_create_tol + rpgp_lowrank_grad_prepare at one tolerance): the product
     (RPGP_OP_LOWRANK) and the derivative (rpgp_bilinear_grad_lowrank) of the same low-rank form.  p, q: ranks (0: not served).
     `max_rank`: the largest p and q served; 64 is rpgp_lowrank_create_tol's plan, above it (up to 128) the plan comes from
-    rpgp_lowrank_create_cap with its buffers sized for the cap, and needs a prepared buffer with a finite max_abs."""
+    rpgp_lowrank_create_cap with its buffers sized for the cap, and needs a prepared buffer with a finite max_abs.
+    `panels`: where that single-interval plan is not served under the cap, build the panel plan of rpgp_lowrank_create_panels
+    instead (any half-width up to about 100 at ranks <= 64 per panel; finite prepared coordinates): `panels` is then its panel
+    count P >= 2 (0: a single-interval plan or none), `h_p` the panel half-width, p and q the ranks inside a panel."""
 
-    def __init__(self, prep, tol, max_rank=64):
-        import ctypes
-        import math
-        lib = _lib.load()
+    def __init__(self, prep, tol, max_rank=64, panels=False):
         max_rank = int(max_rank)
         if not 1 <= max_rank <= LOWRANK_KERNEL_RANK:
             raise ValueError("LowrankTrainPlan: max_rank = %r outside 1 ... %d" % (max_rank, LOWRANK_KERNEL_RANK))
@@ -300,6 +320,51 @@ class LowrankTrainPlan:
         self.max_rank = max_rank
         self.p = self.q = 0
         self.handle = None
+        self.panels, self.h_p = 0, None
+        self.want_panels = bool(panels)
+        if max_rank > 64 or prep.fast_ok or not panels:    # (at 64 the single interval is the fast_ok plan)
+            self._single_interval(prep, max_rank)
+        if panels and not self.served:
+            self._panel_plan(prep)
+
+    def _panel_plan(self, prep):
+        import ctypes
+        import math
+        lib = _lib.load()
+        if self.handle:                                   # (a product rank without a derivative rank: not the plan that serves)
+            lib.rpgp_lowrank_destroy(self.handle)
+        self.p = self.q = 0
+        self.handle = None
+        if prep.buf is None or not math.isfinite(prep.max_abs) or not self.tol > 0.0:
+            return
+        if not prep.fast_ok:                              # (as above the cap of 64: the prepared coordinates decide)
+            rowdat = prep.buf[512:512 + 8 * self.N * self.J].view(torch.float32)
+            if not bool(torch.isfinite(rowdat).all()):
+                return
+        with _on(prep.device):
+            self._plan = torch.empty(int(lib.rpgp_lowrank_panels_plan_bytes(self.N, self.J)), dtype=torch.uint8,
+                                     device=self.device)
+            P, p, h = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_void_p(None)
+            _lib.check(lib.rpgp_lowrank_create_panels(prep.buf.data_ptr(), self.N, self.J, prep.max_abs, self.tol, 0,
+                                                      self._plan.data_ptr(), self._plan.numel(), ctypes.byref(P),
+                                                      ctypes.byref(p), ctypes.byref(h), _stream()),
+                       "rpgp_lowrank_create_panels")
+            if not P.value:
+                self._plan = None
+                return
+            self.handle = h.value
+            self._dcoef = torch.empty(int(lib.rpgp_lowrank_grad_bytes(self.handle)), dtype=torch.uint8, device=self.device)
+            q, hp = ctypes.c_int(0), ctypes.c_double(0.0)
+            _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(), self._dcoef.numel(),
+                                                     ctypes.byref(q), _stream()), "rpgp_lowrank_grad_prepare")
+            _lib.check(lib.rpgp_lowrank_panels_info(self.handle, None, ctypes.byref(hp), None, None, None),
+                       "rpgp_lowrank_panels_info")
+        self.panels, self.h_p, self.p, self.q = int(P.value), float(hp.value), int(p.value), int(q.value)
+
+    def _single_interval(self, prep, max_rank):
+        import ctypes
+        import math
+        lib = _lib.load()
         if max_rank > 64:
             if prep.buf is None or not math.isfinite(prep.max_abs):
                 return                                    # no prepared coordinates, or a Z with an Inf: not served
@@ -350,17 +415,19 @@ class LowrankTrainPlan:
             self.handle = None
 
 
-def lowrank_train_plan(prep, scale, noise, mass=None, max_rank=64):
+def lowrank_train_plan(prep, scale, noise, mass=None, max_rank=64, panels=False):
     """The training plan of `prep` for this step's (N, scale, noise), or None when the low-rank form does not serve it (switch
     off, no tolerance, p or q above max_rank; at max_rank 64 a Z that is not fast_ok, above it one without prepared coordinates
     or with a non-finite max_abs: the Chebyshev form evaluates no exponential, so the sweep's exp2 range guard does not bind
     it).  Built once per Prepared, tolerance and cap.  `mass`: the kernel's diagonal mass when it is not scale * J — scale *
-    sum_c |w_c| of a weighted family operator, so that lowrank_train_tol's spectral bound holds for it."""
+    sum_c |w_c| of a weighted family operator, so that lowrank_train_tol's spectral bound holds for it.  `panels`
+    (settings.lowrank_panels): where the single-interval plan is not served under max_rank, the panel plan, which needs what
+    a cap above 64 needs."""
     import math
     max_rank = int(max_rank)
     if not lowrank_enabled():
         return None
-    if max_rank <= 64:
+    if max_rank <= 64 and not panels:
         if not prep.fast_ok:
             return None
     elif prep.buf is None or not math.isfinite(prep.max_abs):
@@ -369,8 +436,12 @@ def lowrank_train_plan(prep, scale, noise, mass=None, max_rank=64):
     if not tol:
         return None
     cached = getattr(prep, "_train", None)
-    if cached is None or cached.tol != tol or getattr(cached, "max_rank", 64) != max_rank:
-        cached = prep._train = LowrankTrainPlan(prep, tol) if max_rank == 64 else LowrankTrainPlan(prep, tol, max_rank)
+    if cached is None or cached.tol != tol or getattr(cached, "max_rank", 64) != max_rank or \
+            getattr(cached, "want_panels", False) != bool(panels):
+        if panels:
+            cached = prep._train = LowrankTrainPlan(prep, tol, max_rank, panels=True)
+        else:
+            cached = prep._train = LowrankTrainPlan(prep, tol) if max_rank == 64 else LowrankTrainPlan(prep, tol, max_rank)
     return cached if cached.served else None
 
 

@@ -255,6 +255,8 @@ def build_parser():
                    help="(rpgp) train on the closed-form marginal likelihood of the Chebyshev low-rank features where served")
     p.add_argument("--lowrank_max_rank", type=int, default=64, metavar="N",
                    help="(rpgp) largest Chebyshev rank served by --lowrank_kernel / --lowrank_posterior / --lowrank_mll (1 ... 128, default 64)")
+    p.add_argument("--lowrank_panels", action="store_true",
+                   help="(rpgp) with --lowrank_kernel: serve half-widths beyond the rank cap (up to about 100) through the panel plan")
     return p
 
 
@@ -409,7 +411,8 @@ def main(argv=None, rank_entry=None):
                 settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)), \
                 settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)), \
                 settings.lowrank_mll(getattr(args, "lowrank_mll", False)), \
-                settings.lowrank_max_rank(getattr(args, "lowrank_max_rank", 64)):
+                settings.lowrank_max_rank(getattr(args, "lowrank_max_rank", 64)), \
+                settings.lowrank_panels(getattr(args, "lowrank_panels", False)):
             if args.ablation:
                 if args.k is not None:
                     abl_vars = args.k

@@ -141,6 +141,13 @@ native_sharded_cg = _setting("native_sharded_cg", True, flag=True)
 # (1e-3 noise / (scale sum_c |w_c| N)): the solve through RPGP_OP_LOWRANK_FAMILY, the derivative by
 # rpgp_bilinear_grad_lowrank_weighted.  Mixed group sizes, SKI, k > 1 and the other sub-kernels keep the family sweep.
 lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
+# ... and where the single-interval plan is not served under lowrank_max_rank (from a half-width of about 6.5 at the cap of 64,
+# about 13 at 128), the panel plan of rpgp_lowrank_create_panels: the interval cut into P = 2 ... 16 equal panels of half-width
+# 3.2 ... 7.7, points of one panel and of neighbouring panels interacting through Chebyshev forms of rank <= 64, points further
+# apart (at least a panel width: below the tolerance) dropped.  Served: half-widths up to about 100 (16 panels), a Z whose
+# prepared coordinates are finite (the sweep's range guard does not bind it), plain and weighted operators alike, the solve and
+# the derivative on the same panels.  Off (the default): every path is the one above, bit for bit.  DESIGN.md 7.9.
+lowrank_panels = _setting("lowrank_panels", False, flag=True)
 # prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
 # with a float64 twin (k = 1, no grid), J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default, up to 128), at most 4096
 # features in 25 % of the device memory gets its posterior mean, covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
