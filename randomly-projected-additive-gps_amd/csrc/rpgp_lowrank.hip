@@ -448,22 +448,12 @@ __global__ __launch_bounds__(256) void lr_output_kernel(const float *__restrict_
   out[(size_t)i * T + t] = res;
 }
 
-template <int PB>
-int launch_lowrank(const LowrankPlan &P, const float *V, float *out, int N, int T, int j0, int jn, int r0, int r1,
-                   float scale, float noise, double *part, float *U, hipStream_t st) {
-  const int nblk = proj_blocks(N);
-  hipLaunchKernelGGL(lr_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, V, part, N, T, j0, jn);
-  hipLaunchKernelGGL(lr_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, U, nblk, T, jn, scale);
-  hipLaunchKernelGGL(lr_output_kernel<PB>, dim3((N + kOutRows - 1) / kOutRows, T), dim3(256), 0, st, P.xt, U, V, out, N, T,
-                     j0, jn, r0, r1, noise);
-  return (int)hipGetLastError();
-}
-
 // ---- per-component weights (rpgp_mvm_sym_lowrank_weighted: the RBF, group-1 members of rpgp_family) ---------------------------
 // K = scale sum_j w_j K_j is linear in the weights and every K_j shares the plan's one form, so w_j enters the product in
 // exactly one place: pass (b) of projection j.  The kernels below are lr_combine_kernel, lrg_combine_kernel and
 // lrg_output_kernel with that factor (and, for the derivative, one sum per component in place of the single gscale); they are
 // kernels of their own, not a template argument of the unweighted ones, so that those keep their names and their code.
+// Every launcher takes the weights as a nullable pointer and launches these kernels when it is given one.
 //
 // (b) U[jj][t][m] = (scale w[j0 + jj]) * sum_n c_mn W[n]: lr_combine_kernel's loads, block-partial order, chunking and single
 // round trip, with the weight requested beside the partials and the factor scale * w formed in float64 (w = 1: the same bits).
@@ -535,14 +525,18 @@ __global__ __launch_bounds__(256) void lrw_combine_kernel(const double *__restri
   }
 }
 
+// the product at a padded rank up to 64.  w: the weights (rpgp_mvm_sym_lowrank_weighted) or null; [r0, r1): the rows written
 template <int PB>
-int launch_lowrank_weighted(const LowrankPlan &P, const float *w, const float *V, float *out, int N, int T, int j0, int jn,
-                            float scale, float noise, double *part, float *U, hipStream_t st) {
+int launch_lowrank(const LowrankPlan &P, const float *w, const float *V, float *out, int N, int T, int j0, int jn, int r0,
+                   int r1, float scale, float noise, double *part, float *U, hipStream_t st) {
   const int nblk = proj_blocks(N);
   hipLaunchKernelGGL(lr_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, V, part, N, T, j0, jn);
-  hipLaunchKernelGGL(lrw_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, w + j0, U, nblk, T, jn, scale);
+  if (w)
+    hipLaunchKernelGGL(lrw_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, w + j0, U, nblk, T, jn, scale);
+  else
+    hipLaunchKernelGGL(lr_combine_kernel<PB>, dim3(jn, T), dim3(256), 0, st, part, P.coef, U, nblk, T, jn, scale);
   hipLaunchKernelGGL(lr_output_kernel<PB>, dim3((N + kOutRows - 1) / kOutRows, T), dim3(256), 0, st, P.xt, U, V, out, N, T,
-                     j0, jn, 0, N, noise);
+                     j0, jn, r0, r1, noise);
   return (int)hipGetLastError();
 }
 
@@ -715,22 +709,6 @@ inline size_t grad_ws_bytes(const LowrankPlan &P, int64_t N, int jn, int T) {
   return ((size_t)proj_blocks(N) * jn * T * grad_pb(P) * 2 + (size_t)jn * T * 2 * P.qb + (size_t)jn * T) * sizeof(double);
 }
 
-template <int PB, int QB>
-int launch_grad(const LowrankPlan &P, const float *L, const float *R, float *gZ, float *gscale, int N, int ldg, int T,
-                int j0, int jn, float scale, void *ws, hipStream_t st) {
-  const int nblk = proj_blocks(N);
-  const size_t np = (size_t)nblk * jn * T * PB;
-  double *partL = reinterpret_cast<double *>(ws), *partR = partL + np;
-  double *U = partR + np, *gsp = U + (size_t)jn * T * 2 * QB;
-  hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, L, partL, N, T, j0, jn);
-  hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, R, partR, N, T, j0, jn);
-  hipLaunchKernelGGL((lrg_combine_kernel<PB, QB>), dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, U, gsp, nblk, T,
-                     jn, P.p, P.pb, (double)scale);
-  hipLaunchKernelGGL(lrg_output_kernel<QB>, dim3((N + kOutRows - 1) / kOutRows), dim3(256), 0, st, P.xt, U, gsp, L, R, gZ,
-                     gscale, N, T, j0, jn, ldg);
-  return (int)hipGetLastError();
-}
-
 // The weighted derivative (rpgp_bilinear_grad_lowrank_weighted).  (b) is lrg_combine_kernel with U^R, U^L carrying
 // scale * w[j0 + jj] (float64; w = 1: the same bits) and gsp left as it is, the UNWEIGHTED W^L^T C W^R of the component.
 // `w` points at the weight of projection j0.
@@ -845,19 +823,26 @@ __global__ __launch_bounds__(256) void lrgw_output_kernel(const float *__restric
   }
 }
 
+// the derivative at padded ranks up to 64.  w: the weights (gout = gcomp) or null (gout = gscale)
 template <int PB, int QB>
-int launch_grad_weighted(const LowrankPlan &P, const float *w, const float *L, const float *R, float *gZ, float *gcomp, int N,
-                         int T, int j0, int jn, float scale, void *ws, hipStream_t st) {
+int launch_grad(const LowrankPlan &P, const float *w, const float *L, const float *R, float *gZ, float *gout, int N, int ldg,
+                int T, int j0, int jn, float scale, void *ws, hipStream_t st) {
   const int nblk = proj_blocks(N);
   const size_t np = (size_t)nblk * jn * T * PB;
   double *partL = reinterpret_cast<double *>(ws), *partR = partL + np;
   double *U = partR + np, *gsp = U + (size_t)jn * T * 2 * QB;
+  const dim3 rows((N + kOutRows - 1) / kOutRows);
   hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, L, partL, N, T, j0, jn);
   hipLaunchKernelGGL(lrg_project_kernel<PB>, dim3(nblk, jn, T), dim3(256), 0, st, P.xt, R, partR, N, T, j0, jn);
-  hipLaunchKernelGGL((lrgw_combine_kernel<PB, QB>), dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, w + j0, U, gsp,
-                     nblk, T, jn, P.p, P.pb, (double)scale);
-  hipLaunchKernelGGL(lrgw_output_kernel<QB>, dim3((N + kOutRows - 1) / kOutRows), dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gcomp,
-                     N, T, j0, jn, P.J);
+  if (w) {
+    hipLaunchKernelGGL((lrgw_combine_kernel<PB, QB>), dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, w + j0, U,
+                       gsp, nblk, T, jn, P.p, P.pb, (double)scale);
+    hipLaunchKernelGGL(lrgw_output_kernel<QB>, rows, dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gout, N, T, j0, jn, ldg);
+  } else {
+    hipLaunchKernelGGL((lrg_combine_kernel<PB, QB>), dim3(jn, T), dim3(256), 0, st, partL, partR, P.dcoef, P.ccoef, U, gsp, nblk,
+                       T, jn, P.p, P.pb, (double)scale);
+    hipLaunchKernelGGL(lrg_output_kernel<QB>, rows, dim3(256), 0, st, P.xt, U, gsp, L, R, gZ, gout, N, T, j0, jn, ldg);
+  }
   return (int)hipGetLastError();
 }
 
@@ -1656,7 +1641,7 @@ int select_to_host(double h, int p_max, double tol, bool deriv, int *p_host, dou
 }
 
 
-// the plan of rpgp_lowrank_create / rpgp_lowrank_create_tol
+// the plan of rpgp_lowrank_create and of rpgp_lowrank_create_cap (rpgp_lowrank_create_tol: that entry at the cap 64)
 int create_plan(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes, int *p_host,
                 void **handle_host, void *stream, int cap = kMaxRank) {
   if (!prep || !plan || !p_host || !handle_host || N <= 0 || N > 0x7fffffffLL || J <= 0 || J > kPrepMaxJ)
@@ -2338,6 +2323,56 @@ int create_panel_plan(const void *prep, int64_t N, int J, float max_abs, double 
   return 0;
 }
 
+// ---- the launch of a plan of any kind: panels, a padded rank above 64, a padded rank up to 64 -----------------------------------
+// The extern "C" entries check their own arguments and workspace size and then call these two.  w: the weights or null.
+
+// rows [r0, r1) of the product (all of them unless the call is pair-sharded); the workspace holds J columns
+int product(const LowrankPlan &P, const float *w, const float *V, float *out, int N, int T, int j0, int jn, int r0, int r1,
+            float scale, float noise, void *workspace, hipStream_t st) {
+  const bool prof = rpgp_internal::prof_open(st);
+  int rc;
+  if (P.panels) {
+    rc = launch_panels(P, w, V, out, N, T, j0, jn, r0, r1, scale, noise, workspace, st);
+  } else {
+    double *part = reinterpret_cast<double *>(workspace);
+    float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P.pb);
+    rc = dispatch_pb<kCapRank>(P.pb, [&](auto pb) {
+      constexpr int PB = decltype(pb)::value;
+      if constexpr (PB <= kMaxRank)
+        return launch_lowrank<PB>(P, w, V, out, N, T, j0, jn, r0, r1, scale, noise, part, U, st);
+      else
+        return launch_lowrank_wide<PB>(P, w, V, out, N, T, j0, jn, r0, r1, scale, noise, part, U, st);
+    });
+  }
+  if (prof) {
+    const int pc = rpgp_internal::prof_close(st);
+    if (!rc) rc = pc;
+  }
+  return rc;
+}
+
+// workspace of the derivative of jn columns
+inline size_t derivative_ws_bytes(const LowrankPlan &P, int64_t N, int jn, int T) {
+  return P.panels ? panel_grad_ws_bytes(P, jn, T) : grad_ws_bytes(P, N, jn, T);
+}
+
+// gout: gcomp with weights, gscale without
+int derivative(const LowrankPlan &P, const float *w, const float *L, const float *R, float *gZ, float *gout, int N, int ldg,
+               int T, int j0, int jn, float scale, void *workspace, hipStream_t st) {
+  if (P.panels) return launch_panels_grad(P, w, L, R, gZ, gout, N, ldg, T, j0, jn, scale, workspace, st);
+  if (grad_pb(P) > kMaxRank) return launch_grad_wide(P, w, L, R, gZ, gout, N, ldg, T, j0, jn, scale, workspace, st);
+  // (PB < QB never occurs: PB = pad8(max(p, q)) >= QB, so no such kernel is instantiated)
+  return dispatch_pb<kMaxRank>(P.qb, [&](auto qb) {
+    return dispatch_pb<kMaxRank>(grad_pb(P), [&](auto pb) -> int {
+      constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;
+      if constexpr (PB >= QB)
+        return launch_grad<PB, QB>(P, w, L, R, gZ, gout, N, ldg, T, j0, jn, scale, workspace, st);
+      else
+        return RPGP_EINVAL;
+    });
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -2430,8 +2465,7 @@ int rpgp_lowrank_create(const void *prep, int64_t N, int J, float max_abs, void 
 
 int rpgp_lowrank_create_tol(const void *prep, int64_t N, int J, float max_abs, double tol, void *plan, size_t plan_bytes,
                             int *p_host, void **handle_host, void *stream) {
-  if (!(tol > 0.0)) return RPGP_EINVAL;
-  return create_plan(prep, N, J, max_abs, tol < kTailTol ? tol : kTailTol, plan, plan_bytes, p_host, handle_host, stream);
+  return rpgp_lowrank_create_cap(prep, N, J, max_abs, tol, kMaxRank, plan, plan_bytes, p_host, handle_host, stream);
 }
 
 int rpgp_lowrank_destroy(void *handle) {
@@ -2456,34 +2490,10 @@ int rpgp_mvm_sym_lowrank_range(const void *handle, const void *prep, const float
   if (world < 1 || rank < 0 || rank >= world) return RPGP_EINVAL;
   const size_t need = rpgp_mvm_sym_lowrank_workspace_bytes(handle, N, T);
   if (!workspace || workspace_bytes < need) return RPGP_EWORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int n = (int)N, jn = j1 - j0;
+  const int n = (int)N;
   // a rank of a pair-sharded call writes its row slice of K v (and the noise term, if it was given one, on every row)
   const int r0 = (int)((int64_t)n * rank / world), r1 = (int)((int64_t)n * (rank + 1) / world);
-  if (P->panels) {
-    const bool prof = rpgp_internal::prof_open(st);
-    int rc = launch_panels(*P, nullptr, V, out, n, T, j0, jn, r0, r1, scale, noise, workspace, st);
-    if (prof) {
-      const int pc = rpgp_internal::prof_close(st);
-      if (!rc) rc = pc;
-    }
-    return rc;
-  }
-  double *part = reinterpret_cast<double *>(workspace);
-  float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
-  const bool prof = rpgp_internal::prof_open(st);
-  int rc = dispatch_pb<kCapRank>(P->pb, [&](auto pb) {
-    constexpr int PB = decltype(pb)::value;
-    if constexpr (PB <= kMaxRank)
-      return launch_lowrank<PB>(*P, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st);
-    else
-      return launch_lowrank_wide<PB>(*P, nullptr, V, out, n, T, j0, jn, r0, r1, scale, noise, part, U, st);
-  });
-  if (prof) {
-    const int pc = rpgp_internal::prof_close(st);
-    if (!rc) rc = pc;
-  }
-  return rc;
+  return product(*P, nullptr, V, out, n, T, j0, j1 - j0, r0, r1, scale, noise, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
 int rpgp_lowrank_grad_select(double h, int q_max, double tol, int *q_host, double *tail_host, double *coef_host) {
@@ -2529,8 +2539,7 @@ int rpgp_lowrank_grad_prepare(void *handle, double tol, void *dcoef, size_t dcoe
 size_t rpgp_bilinear_grad_lowrank_workspace_bytes(const void *handle, int64_t N, int T) {
   const LowrankPlan *P = reinterpret_cast<const LowrankPlan *>(handle);
   if (!P || !P->q || N <= 0 || N > 0x7fffffffLL || T <= 0) return 0;
-  if (P->panels) return panel_grad_ws_bytes(*P, P->J, T);
-  return grad_ws_bytes(*P, N, P->J, T);
+  return derivative_ws_bytes(*P, N, P->J, T);
 }
 
 int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *R, float *gZ, float *gscale, int64_t N,
@@ -2540,26 +2549,9 @@ int rpgp_bilinear_grad_lowrank(const void *handle, const float *L, const float *
   if (!P || !L || !R || !gZ || !gscale || N <= 0 || T <= 0 || T > 65535) return RPGP_EINVAL;
   if (N != P->N || j0 < 0 || j1 <= j0 || j1 > P->J || ldg < P->J) return RPGP_EINVAL;
   if (!P->q) return RPGP_EINVAL;                          // no derivative rank: the caller runs rpgp_bilinear_grad
-  if (P->panels) {
-    if (!workspace || workspace_bytes < panel_grad_ws_bytes(*P, j1 - j0, T)) return RPGP_EWORKSPACE;
-    return launch_panels_grad(*P, nullptr, L, R, gZ, gscale, (int)N, ldg, T, j0, j1 - j0, scale, workspace,
-                              reinterpret_cast<hipStream_t>(stream));
-  }
-  if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int n = (int)N, jn = j1 - j0;
-  if (grad_pb(*P) > kMaxRank)
-    return launch_grad_wide(*P, nullptr, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st);
-  // (PB < QB never occurs: PB = pad8(max(p, q)) >= QB, so no such kernel is instantiated)
-  return dispatch_pb<kMaxRank>(P->qb, [&](auto qb) {
-    return dispatch_pb<kMaxRank>(grad_pb(*P), [&](auto pb) -> int {
-      constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;
-      if constexpr (PB >= QB)
-        return launch_grad<PB, QB>(*P, L, R, gZ, gscale, n, ldg, T, j0, jn, scale, workspace, st);
-      else
-        return RPGP_EINVAL;
-    });
-  });
+  if (!workspace || workspace_bytes < derivative_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
+  return derivative(*P, nullptr, L, R, gZ, gscale, (int)N, ldg, T, j0, j1 - j0, scale, workspace,
+                    reinterpret_cast<hipStream_t>(stream));
 }
 
 int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const float *weights, const float *V, float *out,
@@ -2571,32 +2563,8 @@ int rpgp_mvm_sym_lowrank_weighted(const void *handle, const void *prep, const fl
   if (N != P->N || J != P->J || T > 65535) return RPGP_EINVAL;
   const size_t need = rpgp_mvm_sym_lowrank_workspace_bytes(handle, N, T);
   if (!workspace || workspace_bytes < need) return RPGP_EWORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int n = (int)N, jn = j1 - j0;
-  if (P->panels) {
-    const bool prof = rpgp_internal::prof_open(st);
-    int rc = launch_panels(*P, weights, V, out, n, T, j0, jn, 0, n, scale, noise, workspace, st);
-    if (prof) {
-      const int pc = rpgp_internal::prof_close(st);
-      if (!rc) rc = pc;
-    }
-    return rc;
-  }
-  double *part = reinterpret_cast<double *>(workspace);
-  float *U = reinterpret_cast<float *>(part + (size_t)proj_blocks(N) * jn * T * P->pb);
-  const bool prof = rpgp_internal::prof_open(st);
-  int rc = dispatch_pb<kCapRank>(P->pb, [&](auto pb) {
-    constexpr int PB = decltype(pb)::value;
-    if constexpr (PB <= kMaxRank)
-      return launch_lowrank_weighted<PB>(*P, weights, V, out, n, T, j0, jn, scale, noise, part, U, st);
-    else
-      return launch_lowrank_wide<PB>(*P, weights, V, out, n, T, j0, jn, 0, n, scale, noise, part, U, st);
-  });
-  if (prof) {
-    const int pc = rpgp_internal::prof_close(st);
-    if (!rc) rc = pc;
-  }
-  return rc;
+  const int n = (int)N;
+  return product(*P, weights, V, out, n, T, j0, j1 - j0, 0, n, scale, noise, workspace, reinterpret_cast<hipStream_t>(stream));
 }
 
 int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights, const float *L, const float *R, float *gZ,
@@ -2606,25 +2574,9 @@ int rpgp_bilinear_grad_lowrank_weighted(const void *handle, const float *weights
   if (!P || !weights || !L || !R || !gZ || !gcomp || N <= 0 || T <= 0 || T > 65535) return RPGP_EINVAL;
   if (N != P->N || J != P->J || j0 < 0 || j1 <= j0 || j1 > J) return RPGP_EINVAL;
   if (!P->q) return RPGP_EINVAL;                          // no derivative rank: the caller runs rpgp_family_bilinear_grad
-  if (P->panels) {
-    if (!workspace || workspace_bytes < panel_grad_ws_bytes(*P, j1 - j0, T)) return RPGP_EWORKSPACE;
-    return launch_panels_grad(*P, weights, L, R, gZ, gcomp, (int)N, P->J, T, j0, j1 - j0, scale, workspace,
-                              reinterpret_cast<hipStream_t>(stream));
-  }
-  if (!workspace || workspace_bytes < grad_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int n = (int)N, jn = j1 - j0;
-  if (grad_pb(*P) > kMaxRank)
-    return launch_grad_wide(*P, weights, L, R, gZ, gcomp, n, P->J, T, j0, jn, scale, workspace, st);
-  return dispatch_pb<kMaxRank>(P->qb, [&](auto qb) {
-    return dispatch_pb<kMaxRank>(grad_pb(*P), [&](auto pb) -> int {
-      constexpr int QB = decltype(qb)::value, PB = decltype(pb)::value;
-      if constexpr (PB >= QB)
-        return launch_grad_weighted<PB, QB>(*P, weights, L, R, gZ, gcomp, n, T, j0, jn, scale, workspace, st);
-      else
-        return RPGP_EINVAL;
-    });
-  });
+  if (!workspace || workspace_bytes < derivative_ws_bytes(*P, N, j1 - j0, T)) return RPGP_EWORKSPACE;
+  return derivative(*P, weights, L, R, gZ, gcomp, (int)N, P->J, T, j0, j1 - j0, scale, workspace,
+                    reinterpret_cast<hipStream_t>(stream));
 }
 
 int rpgp_lowrank_post_select(double h, double tol, int p_max, int *p_host, int *r_host, double *tail_host, double *G_host) {

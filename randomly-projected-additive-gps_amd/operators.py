@@ -13,18 +13,24 @@ from .hostvals import host_float
 from . import settings
 
 
-def _panels_keyword(plan_fn):
-    """{"panels": True} for a backend's lowrank_train_plan under settings.lowrank_panels, {} with the setting off (the call is
-    then today's) or for a backend whose plan function does not take the keyword: no panels."""
-    if not settings.lowrank_panels.on():
-        return {}
-    import inspect
-    try:
-        params = inspect.signature(plan_fn).parameters
-    except (TypeError, ValueError):
-        return {}
-    takes = "panels" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
-    return {"panels": True} if takes else {}
+def _plan_keywords(plan_fn):
+    """The keywords of a backend's lowrank_train_plan(prep, scale, noise[, mass=...]) under the settings.  At the defaults there
+    are none, so that a backend written against the older signature keeps working: `max_rank` is passed only above 64 (64 is
+    the plan's own cap), `panels=True` only under settings.lowrank_panels and to a plan function that takes the keyword (one
+    that does not: no panels)."""
+    kw = {}
+    cap = settings.lowrank_max_rank.value()
+    if cap > 64:
+        kw["max_rank"] = cap
+    if settings.lowrank_panels.on():
+        import inspect
+        try:
+            params = inspect.signature(plan_fn).parameters
+        except (TypeError, ValueError):
+            params = {}
+        if "panels" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
+            kw["panels"] = True
+    return kw
 
 
 class LinearOperator:
@@ -202,23 +208,38 @@ class AdditiveRPOperator(LinearOperator):
         N, the scale and the noise (default: the host value the marginal likelihood recorded), so that the solve and the
         derivative of a step use the same form.  Ranks p, q up to settings.lowrank_max_rank (64 by default; above it a Z
         beyond the factorised sweep's range guard is served too, and its Python-path products run the direct sweep)."""
+        return self._decide_lowrank(noise, lambda be, noise: type(self) is AdditiveRPOperator and
+                                    (self.shard is None or self.shard.world_size <= 1))
+
+    def _decide_lowrank(self, noise, mine, mass=None, sweep_guard=False):
+        """lowrank_form of this class and of its weighted subclass.  `mine(be, noise)`: the class's own conditions (its exact type
+        first), asked once the setting is on and the noise is known, before the shared ones: a symmetric float32 operator with
+        J <= 64 and a backend with prepare and lowrank_train_plan.  `mass()`: the diagonal mass passed as mass=, read (one host
+        sync) only when a plan is asked for.  `sweep_guard`: at the default cap without panels a Z that is not fast_ok asks for
+        no plan."""
         if getattr(self, "_lowrank", None) is None:
             self._lowrank = False
             be = _backend.get_backend()
             plan_fn, prepare = getattr(be, "lowrank_train_plan", None), getattr(be, "prepare", None)
             if noise is None:
                 noise = getattr(self, "_noise_host", None)
-            if settings.lowrank_kernel.on() and type(self) is AdditiveRPOperator and self.symmetric and \
-                    (self.shard is None or self.shard.world_size <= 1) and self.Z1.dtype == torch.float32 and \
-                    plan_fn is not None and prepare is not None and noise is not None and self.num_projections <= 64:
+            if settings.lowrank_kernel.on() and noise is not None and mine(be, noise) and self.symmetric and \
+                    self.Z1.dtype == torch.float32 and self.num_projections <= 64 and plan_fn is not None and \
+                    prepare is not None:
                 if self._prep is None:
                     self._prep = prepare(self.Z1.detach())
-                cap = settings.lowrank_max_rank.value()     # (passed on only above the default: 64 is the plan's own)
-                plan = plan_fn(self._prep, self._scale, float(noise), **({"max_rank": cap} if cap > 64 else {}),
-                               **_panels_keyword(plan_fn))
-                if plan is not None:
-                    self._lowrank = plan
+                kw = _plan_keywords(plan_fn)
+                if self._prep.fast_ok or kw or not sweep_guard:
+                    if mass is not None:
+                        kw = dict(mass=mass(), **kw)
+                    plan = plan_fn(self._prep, self._scale, float(noise), **kw)
+                    if plan is not None:
+                        self._lowrank = plan
         return self._lowrank or None
+
+    def _lowrank_in_use(self, noise=None):
+        """lowrank_form(noise) under settings.lowrank_kernel or once a plan serves this operator, else None without deciding."""
+        return self.lowrank_form(noise) if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
 
     def lowrank_mll_form(self, noise=None):
         """The explicit features (lowrank_mll.FeatureForm) on which settings.lowrank_mll evaluates this operator's marginal
@@ -274,7 +295,7 @@ class AdditiveRPOperator(LinearOperator):
             return None
         from . import _lib
         z1 = self.Z1.detach()
-        lr = self.lowrank_form(noise) if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        lr = self._lowrank_in_use(noise)
         if lr is not None:
             return be.make_operator_desc(_lib.RPGP_OP_LOWRANK, z1.shape[0], z1.shape[1], self._scale, noise, lowrank=lr)
         j0, j1 = self._jrange()
@@ -358,7 +379,7 @@ class AdditiveRPOperator(LinearOperator):
             raise NotImplementedError("derivatives are only needed for the train-train kernel")
         be = _backend.get_backend()
         j0, j1 = self._jrange()
-        lr = self.lowrank_form() if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        lr = self._lowrank_in_use()
         if lr is not None:
             gZ, gs = be.bilinear_grad_lowrank(lr, left_vecs.detach(), right_vecs.detach(), self._scale)
         elif j1 > j0:
@@ -859,28 +880,14 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         symmetric float32 RBF operator with k = 1 and J <= 64, a backend with the weighted entries, a known positive noise and
         a plan with p, q <= settings.lowrank_max_rank (64 by default) at the tolerance of the kernel's diagonal mass scale * sum_c |w_c| (weights of any sign: the
         product is linear in them).  Decided ONCE per operator, like the plain operator's."""
-        if getattr(self, "_lowrank", None) is None:
-            self._lowrank = False
-            be = _backend.get_backend()
-            plan_fn, prepare = getattr(be, "lowrank_train_plan", None), getattr(be, "prepare", None)
-            if noise is None:
-                noise = getattr(self, "_noise_host", None)
-            if settings.lowrank_kernel.on() and type(self) is FamilyAdditiveOperator and self.symmetric and \
-                    self.Z1.dtype == torch.float32 and self.kind == "RBF" and self.group == 1 and not self.product and \
-                    not self._generic and self.num_projections <= 64 and plan_fn is not None and prepare is not None and \
-                    hasattr(be, "mvm_sym_lowrank_weighted") and hasattr(be, "bilinear_grad_lowrank_weighted") and \
-                    noise is not None and float(noise) > 0.0:
-                if self._prep is None:
-                    self._prep = prepare(self.Z1.detach())
-                cap = settings.lowrank_max_rank.value()     # (passed on only above the default: 64 is the plan's own)
-                pk = _panels_keyword(plan_fn)
-                if self._prep.fast_ok or cap > 64 or pk:    # (above 64 the plan decides: a finite range, not the sweep's guard)
-                    wabs = float(self.fam.weights.abs().sum())
-                    plan = plan_fn(self._prep, self._scale, float(noise), mass=self._scale * wabs,
-                                   **({"max_rank": cap} if cap > 64 else {}), **pk)
-                    if plan is not None:
-                        self._lowrank = plan
-        return self._lowrank or None
+        def mine(be, noise):
+            return type(self) is FamilyAdditiveOperator and self.kind == "RBF" and self.group == 1 and not self.product and \
+                not self._generic and hasattr(be, "mvm_sym_lowrank_weighted") and \
+                hasattr(be, "bilinear_grad_lowrank_weighted") and float(noise) > 0.0
+
+        # (sweep_guard: above 64 or with panels the plan decides on a finite range; at the defaults the sweep's guard does)
+        return self._decide_lowrank(noise, mine, mass=lambda: self._scale * float(self.fam.weights.abs().sum()),
+                                    sweep_guard=True)
 
     def _local_matmul(self, rhs, noise=0.0):
         be = _backend.get_backend()
@@ -910,7 +917,7 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         if not self.symmetric or not hasattr(be, "mbcg_solve") or self._generic:
             return None
         from . import _lib
-        lr = self.lowrank_form(noise) if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        lr = self._lowrank_in_use(noise)
         if lr is not None:
             return be.make_operator_desc(_lib.RPGP_OP_LOWRANK_FAMILY, self.Z1.shape[0], self.Z1.shape[1], self._scale, noise,
                                          family=self.fam, lowrank=lr)
@@ -957,7 +964,7 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         if not self.symmetric:
             raise NotImplementedError("derivatives are only needed for the train-train kernel")
         be = _backend.get_backend()
-        lr = self.lowrank_form() if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        lr = self._lowrank_in_use()
         if lr is not None:
             gZ, gc = be.bilinear_grad_lowrank_weighted(lr, self.fam.weights, left_vecs.detach(), right_vecs.detach(),
                                                        self._scale)

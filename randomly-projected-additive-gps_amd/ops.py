@@ -193,6 +193,25 @@ def trace_range(name):
     return _Range(name.encode()) if _RANGES_ON else _NULL_RANGE
 
 
+# rpgp_prepare's buffer (csrc/rpgp_kernels.hip, prep_layout): [header][mid][rowdat: N J float2 {a, Ea}][coldat: N J float2]
+_PREP_HEADER_FLOATS = 64
+_PREP_MID_FLOATS = 64
+_PREP_ROWDAT_BYTE_OFFSET = 4 * (_PREP_HEADER_FLOATS + _PREP_MID_FLOATS)
+_PREP_ROWDAT_BYTES_PER_ENTRY = 8
+
+
+def _lowrank_create(prep, entry, nbytes, *args, nout=1):
+    """(buffer, handle, the entry's int results) of one of the rpgp_lowrank_create* entries on the Prepared `prep`: a plan buffer
+    of `nbytes`, and `args` between max_abs and the buffer.  No handle (the form does not serve this Z): no buffer either."""
+    import ctypes
+    outs, h = [ctypes.c_int(0) for _ in range(nout)], ctypes.c_void_p(None)
+    with _on(prep.device):
+        buf = torch.empty(int(nbytes), dtype=torch.uint8, device=prep.device)
+        _lib.check(getattr(_lib.load(), entry)(prep.buf.data_ptr(), prep.N, prep.J, prep.max_abs, *args, buf.data_ptr(),
+                                               buf.numel(), *[ctypes.byref(o) for o in outs], ctypes.byref(h), _stream()), entry)
+    return (buf if h.value else None), h.value, [int(o.value) for o in outs]
+
+
 class Prepared:
     """Device-side tables of rpgp_prepare for one Z (centred, pre-scaled coordinates for the factorised fast path)."""
 
@@ -226,26 +245,24 @@ class Prepared:
         """Rank p of the low-rank plan of this Z (0: not served — the range needs more than 64 — or not fast_ok).  The plan is
         built on first use, so that a Prepared that only feeds the native solver (which runs the sweep) does not pay for it."""
         if self._rank is None:
-            import ctypes
             self._rank = 0
             if self.fast_ok:
-                lib = _lib.load()
-                with _on(self.device):
-                    self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes(self.N, self.J)), dtype=torch.uint8,
-                                             device=self.device)
-                    p, h = ctypes.c_int(0), ctypes.c_void_p(None)
-                    _lib.check(lib.rpgp_lowrank_create(self.buf.data_ptr(), self.N, self.J, self.max_abs,
-                                                       self._plan.data_ptr(), self._plan.numel(), ctypes.byref(p),
-                                                       ctypes.byref(h), _stream()), "rpgp_lowrank_create")
-                self._rank, self._handle = int(p.value), h.value
-                if not self._rank:
-                    self._plan = None
+                nbytes = _lib.load().rpgp_lowrank_plan_bytes(self.N, self.J)
+                self._plan, self._handle, (self._rank,) = _lowrank_create(self, "rpgp_lowrank_create", nbytes)
         return self._rank
 
     def __del__(self):
         if getattr(self, "_handle", None):
             _lib.load().rpgp_lowrank_destroy(self._handle)
             self._handle = None
+
+
+def _prepared_coordinates_finite(prep):
+    """Whether every prepared coordinate of `prep` is finite: one reduction and one host sync.  What decides for a Z that is
+    not fast_ok, which is beyond the sweep's range guard or holds a NaN (which max_abs skips)."""
+    nbytes = _PREP_ROWDAT_BYTES_PER_ENTRY * prep.N * prep.J
+    rowdat = prep.buf[_PREP_ROWDAT_BYTE_OFFSET:_PREP_ROWDAT_BYTE_OFFSET + nbytes].view(torch.float32)
+    return bool(torch.isfinite(rowdat).all())
 
 
 def lowrank_enabled():
@@ -303,11 +320,22 @@ def lowrank_panels_select(h, tol=_LOWRANK_TAIL, panels=0):
             "C0": c[0, :p, :p].copy(), "C1": c[1, :p, :p].copy(), "D0": c[2, :q, :q].copy(), "D1": c[3, :q, :q].copy()}
 
 
+def _lowrank_plan_eligible(prep, max_rank, panels):
+    """The rule of which Prepared a training plan is built on, before any device call.  At a cap up to 64 without panels: a
+    fast_ok Z, the sweep's own guard.  Above 64 or with panels: prepared coordinates and a finite max_abs (the Chebyshev form
+    evaluates no exponential, so the sweep's exp2 range guard does not bind it); a Z that is not fast_ok must then also pass
+    _prepared_coordinates_finite, which the plan asks once when it is built."""
+    import math
+    if max_rank <= 64 and not panels:
+        return prep.fast_ok
+    return prep.buf is not None and math.isfinite(prep.max_abs)
+
+
 class LowrankTrainPlan:
-    """Training plan of one Prepared (rpgp_lowrank_create_tol + rpgp_lowrank_grad_prepare at one tolerance): the product
+    """Training plan of one Prepared (rpgp_lowrank_create_cap + rpgp_lowrank_grad_prepare at one tolerance): the product
     (RPGP_OP_LOWRANK) and the derivative (rpgp_bilinear_grad_lowrank) of the same low-rank form.  p, q: ranks (0: not served).
-    `max_rank`: the largest p and q served; 64 is rpgp_lowrank_create_tol's plan, above it (up to 128) the plan comes from
-    rpgp_lowrank_create_cap with its buffers sized for the cap, and needs a prepared buffer with a finite max_abs.
+    `max_rank`: the largest p and q served, 1 ... 128, with the plan's buffers sized for it; which Prepared is served at which
+    cap: _lowrank_plan_eligible.
     `panels`: where that single-interval plan is not served under the cap, build the panel plan of rpgp_lowrank_create_panels
     instead (any half-width up to about 100 at ranks <= 64 per panel; finite prepared coordinates): `panels` is then its panel
     count P >= 2 (0: a single-interval plan or none), `h_p` the panel half-width, p and q the ranks inside a panel."""
@@ -322,88 +350,47 @@ class LowrankTrainPlan:
         self.handle = None
         self.panels, self.h_p = 0, None
         self.want_panels = bool(panels)
-        if max_rank > 64 or prep.fast_ok or not panels:    # (at 64 the single interval is the fast_ok plan)
-            self._single_interval(prep, max_rank)
+        if not _lowrank_plan_eligible(prep, max_rank, panels) or not (prep.fast_ok or _prepared_coordinates_finite(prep)):
+            return                                        # not served: no handle, no plan call
+        if max_rank > 64 or prep.fast_ok:                 # (up to 64 the single interval is the fast_ok plan)
+            self._single_interval(prep)
         if panels and not self.served:
             self._panel_plan(prep)
 
+    def _grad_prepare(self):
+        """q of rpgp_lowrank_grad_prepare on the plan's handle, with the derivative's coefficient buffer (0: no derivative rank)."""
+        import ctypes
+        lib = _lib.load()
+        q = ctypes.c_int(0)
+        with _on(self.device):
+            self._dcoef = torch.empty(int(lib.rpgp_lowrank_grad_bytes(self.handle)), dtype=torch.uint8, device=self.device)
+            _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(), self._dcoef.numel(),
+                                                     ctypes.byref(q), _stream()), "rpgp_lowrank_grad_prepare")
+        return int(q.value)
+
+    def _single_interval(self, prep):
+        nbytes = _lib.load().rpgp_lowrank_plan_bytes_cap(self.N, self.J, self.max_rank)
+        self._plan, self.handle, (self.p,) = _lowrank_create(prep, "rpgp_lowrank_create_cap", nbytes, self.tol, self.max_rank)
+        if self.p:
+            self.q = self._grad_prepare()
+
     def _panel_plan(self, prep):
         import ctypes
-        import math
         lib = _lib.load()
         if self.handle:                                   # (a product rank without a derivative rank: not the plan that serves)
             lib.rpgp_lowrank_destroy(self.handle)
         self.p = self.q = 0
         self.handle = None
-        if prep.buf is None or not math.isfinite(prep.max_abs) or not self.tol > 0.0:
+        if not self.tol > 0.0:
             return
-        if not prep.fast_ok:                              # (as above the cap of 64: the prepared coordinates decide)
-            rowdat = prep.buf[512:512 + 8 * self.N * self.J].view(torch.float32)
-            if not bool(torch.isfinite(rowdat).all()):
-                return
-        with _on(prep.device):
-            self._plan = torch.empty(int(lib.rpgp_lowrank_panels_plan_bytes(self.N, self.J)), dtype=torch.uint8,
-                                     device=self.device)
-            P, p, h = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_void_p(None)
-            _lib.check(lib.rpgp_lowrank_create_panels(prep.buf.data_ptr(), self.N, self.J, prep.max_abs, self.tol, 0,
-                                                      self._plan.data_ptr(), self._plan.numel(), ctypes.byref(P),
-                                                      ctypes.byref(p), ctypes.byref(h), _stream()),
-                       "rpgp_lowrank_create_panels")
-            if not P.value:
-                self._plan = None
-                return
-            self.handle = h.value
-            self._dcoef = torch.empty(int(lib.rpgp_lowrank_grad_bytes(self.handle)), dtype=torch.uint8, device=self.device)
-            q, hp = ctypes.c_int(0), ctypes.c_double(0.0)
-            _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(), self._dcoef.numel(),
-                                                     ctypes.byref(q), _stream()), "rpgp_lowrank_grad_prepare")
-            _lib.check(lib.rpgp_lowrank_panels_info(self.handle, None, ctypes.byref(hp), None, None, None),
-                       "rpgp_lowrank_panels_info")
-        self.panels, self.h_p, self.p, self.q = int(P.value), float(hp.value), int(p.value), int(q.value)
-
-    def _single_interval(self, prep, max_rank):
-        import ctypes
-        import math
-        lib = _lib.load()
-        if max_rank > 64:
-            if prep.buf is None or not math.isfinite(prep.max_abs):
-                return                                    # no prepared coordinates, or a Z with an Inf: not served
-            if not prep.fast_ok:
-                # beyond the sweep's range guard, or a NaN (which max_abs skips): the prepared coordinates decide, one
-                # reduction and one host sync per plan (rowdat: N J float2 behind the 128-float header)
-                rowdat = prep.buf[512:512 + 8 * self.N * self.J].view(torch.float32)
-                if not bool(torch.isfinite(rowdat).all()):
-                    return
-            with _on(prep.device):
-                self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes_cap(self.N, self.J, max_rank)), dtype=torch.uint8,
-                                         device=self.device)
-                p, h = ctypes.c_int(0), ctypes.c_void_p(None)
-                _lib.check(lib.rpgp_lowrank_create_cap(prep.buf.data_ptr(), self.N, self.J, prep.max_abs, self.tol, max_rank,
-                                                       self._plan.data_ptr(), self._plan.numel(), ctypes.byref(p),
-                                                       ctypes.byref(h), _stream()), "rpgp_lowrank_create_cap")
-                self.p, self.handle = int(p.value), h.value
-                if self.p:
-                    self._dcoef = torch.empty(int(lib.rpgp_lowrank_grad_bytes(self.handle)), dtype=torch.uint8,
-                                              device=self.device)
-                    q = ctypes.c_int(0)
-                    _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(),
-                                                             self._dcoef.numel(), ctypes.byref(q), _stream()),
-                               "rpgp_lowrank_grad_prepare")
-                    self.q = int(q.value)
+        nbytes = lib.rpgp_lowrank_panels_plan_bytes(self.N, self.J)
+        self._plan, self.handle, (P, p) = _lowrank_create(prep, "rpgp_lowrank_create_panels", nbytes, self.tol, 0, nout=2)
+        if not P:
             return
-        with _on(prep.device):
-            self._plan = torch.empty(int(lib.rpgp_lowrank_plan_bytes(self.N, self.J)), dtype=torch.uint8, device=self.device)
-            p, h = ctypes.c_int(0), ctypes.c_void_p(None)
-            _lib.check(lib.rpgp_lowrank_create_tol(prep.buf.data_ptr(), self.N, self.J, prep.max_abs, self.tol,
-                                                   self._plan.data_ptr(), self._plan.numel(), ctypes.byref(p),
-                                                   ctypes.byref(h), _stream()), "rpgp_lowrank_create_tol")
-            self.p, self.handle = int(p.value), h.value
-            if self.p:
-                self._dcoef = torch.empty(_lib.RPGP_LOWRANK_GRAD_BYTES, dtype=torch.uint8, device=self.device)
-                q = ctypes.c_int(0)
-                _lib.check(lib.rpgp_lowrank_grad_prepare(self.handle, self.tol, self._dcoef.data_ptr(), self._dcoef.numel(),
-                                                         ctypes.byref(q), _stream()), "rpgp_lowrank_grad_prepare")
-                self.q = int(q.value)
+        q, hp = self._grad_prepare(), ctypes.c_double(0.0)
+        _lib.check(lib.rpgp_lowrank_panels_info(self.handle, None, ctypes.byref(hp), None, None, None),
+                   "rpgp_lowrank_panels_info")
+        self.panels, self.h_p, self.p, self.q = P, float(hp.value), p, q
 
     @property
     def served(self):
@@ -417,31 +404,23 @@ class LowrankTrainPlan:
 
 def lowrank_train_plan(prep, scale, noise, mass=None, max_rank=64, panels=False):
     """The training plan of `prep` for this step's (N, scale, noise), or None when the low-rank form does not serve it (switch
-    off, no tolerance, p or q above max_rank; at max_rank 64 a Z that is not fast_ok, above it one without prepared coordinates
-    or with a non-finite max_abs: the Chebyshev form evaluates no exponential, so the sweep's exp2 range guard does not bind
-    it).  Built once per Prepared, tolerance and cap.  `mass`: the kernel's diagonal mass when it is not scale * J — scale *
-    sum_c |w_c| of a weighted family operator, so that lowrank_train_tol's spectral bound holds for it.  `panels`
-    (settings.lowrank_panels): where the single-interval plan is not served under max_rank, the panel plan, which needs what
-    a cap above 64 needs."""
-    import math
-    max_rank = int(max_rank)
-    if not lowrank_enabled():
-        return None
-    if max_rank <= 64 and not panels:
-        if not prep.fast_ok:
-            return None
-    elif prep.buf is None or not math.isfinite(prep.max_abs):
+    off, no tolerance, p or q above max_rank, or a Z that _lowrank_plan_eligible turns away).  Built once per Prepared,
+    tolerance, cap and `panels`.  `mass`: the kernel's diagonal mass when it is not scale * J — scale * sum_c |w_c| of a
+    weighted family operator, so that lowrank_train_tol's spectral bound holds for it.  `panels` (settings.lowrank_panels):
+    where the single-interval plan is not served under max_rank, the panel plan, which needs what a cap above 64 needs."""
+    max_rank, panels = int(max_rank), bool(panels)
+    if not lowrank_enabled() or not _lowrank_plan_eligible(prep, max_rank, panels):
         return None
     tol = lowrank_train_tol(prep.N, prep.J, scale, noise) if mass is None else lowrank_train_tol(prep.N, 1, mass, noise)
     if not tol:
         return None
-    cached = getattr(prep, "_train", None)
-    if cached is None or cached.tol != tol or getattr(cached, "max_rank", 64) != max_rank or \
-            getattr(cached, "want_panels", False) != bool(panels):
-        if panels:
-            cached = prep._train = LowrankTrainPlan(prep, tol, max_rank, panels=True)
-        else:
-            cached = prep._train = LowrankTrainPlan(prep, tol) if max_rank == 64 else LowrankTrainPlan(prep, tol, max_rank)
+    key = (tol, max_rank, panels)
+    cached_key, cached = getattr(prep, "_train", (None, None))
+    if cached_key != key:
+        # (the default cap without panels is the two-argument construction; the keyword is passed only when asked)
+        args = (tol,) if max_rank == 64 and not panels else (tol, max_rank)
+        cached = LowrankTrainPlan(prep, *args, **({"panels": True} if panels else {}))
+        prep._train = (key, cached)
     return cached if cached.served else None
 
 

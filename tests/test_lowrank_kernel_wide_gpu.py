@@ -402,6 +402,65 @@ def test_same_bits_as_a_create_tol_plan_below_the_old_cap(gpu_device, target):
     assert torch.equal(ops.mvm_sym_prepared(prep, L, SCALE, 0.3), _raw_product(new, prep, L, SCALE, 0.3))
 
 
+class _RawPlan:
+    """A plan made at the ctypes level, with what _raw_product and _raw_grad read of a LowrankTrainPlan."""
+
+    def __init__(self, prep, entry, nbytes, *args):
+        from rpgp_amd import _lib, ops
+        self.N, self.J = prep.N, prep.J
+        self.buf = torch.empty(int(nbytes), dtype=torch.uint8, device=prep.device)
+        p, h = ctypes.c_int(0), ctypes.c_void_p(None)
+        rc = getattr(_lib.load(), entry)(prep.buf.data_ptr(), prep.N, prep.J, prep.max_abs, *args, self.buf.data_ptr(),
+                                         self.buf.numel(), ctypes.byref(p), ctypes.byref(h), ops._stream())
+        assert rc == 0, (entry, rc)
+        self.p, self.handle = p.value, h.value
+
+    def grad_prepare(self, tol):
+        from rpgp_amd import _lib, ops
+        lib = _lib.load()
+        self.dcoef = torch.empty(int(lib.rpgp_lowrank_grad_bytes(self.handle)), dtype=torch.uint8, device=self.buf.device)
+        q = ctypes.c_int(0)
+        assert lib.rpgp_lowrank_grad_prepare(self.handle, tol, self.dcoef.data_ptr(), self.dcoef.numel(), ctypes.byref(q),
+                                             ops._stream()) == 0
+        return q.value
+
+
+def test_the_three_creators_give_the_same_plan_at_the_cap_64(gpu_device):
+    """rpgp_lowrank_create, rpgp_lowrank_create_tol at 2^-26 and rpgp_lowrank_create_cap at 2^-26 with the cap 64 on one
+    Prepared, at the ctypes level (ops builds every training plan through the cap entry, so no other test reaches
+    rpgp_lowrank_create_tol): the same p, the same q after rpgp_lowrank_grad_prepare on the last two, and the same bits of the
+    product (all three) and of the derivative (the two with one).  N = 2049: two projection blocks, the smallest N at which
+    the block sum has more than one term."""
+    from rpgp_amd import _lib, ops
+    lib = _lib.load()
+    N, J, T = 2049, 3, 2
+    Z, L, R = _inputs(N, J, T, 3.0, gpu_device, seed=64)
+    prep = ops.Prepared(Z)
+    assert prep.fast_ok
+    plans = [_RawPlan(prep, "rpgp_lowrank_create", lib.rpgp_lowrank_plan_bytes(N, J)),
+             _RawPlan(prep, "rpgp_lowrank_create_tol", lib.rpgp_lowrank_plan_bytes(N, J), TAIL),
+             _RawPlan(prep, "rpgp_lowrank_create_cap", lib.rpgp_lowrank_plan_bytes_cap(N, J, 64), TAIL, 64)]
+    try:
+        print("p %s" % [pl.p for pl in plans])
+        assert 0 < plans[0].p <= 64 and plans[1].p == plans[0].p and plans[2].p == plans[0].p
+        assert all(pl.handle for pl in plans)
+        q = [pl.grad_prepare(TAIL) for pl in plans[1:]]
+        print("q %s" % q)
+        assert 0 < q[0] <= 64 and q[1] == q[0]
+        outs = [_raw_product(pl, prep, L, SCALE, 0.3) for pl in plans]
+        assert torch.isfinite(outs[0]).all() and torch.equal(outs[1], outs[0]) and torch.equal(outs[2], outs[0])
+        grads = []
+        for pl in plans[1:]:
+            gZ, gs = torch.zeros(N, J, device=gpu_device), torch.zeros(1, device=gpu_device)
+            assert _raw_grad(pl, L, R, gZ, gs, 0, J, SCALE) == 0
+            grads.append((gZ, gs))
+        assert torch.isfinite(grads[0][0]).all() and float(grads[0][0].abs().max()) > 0.0
+        assert torch.equal(grads[1][0], grads[0][0]) and torch.equal(grads[1][1], grads[0][1])
+    finally:
+        for pl in plans:
+            lib.rpgp_lowrank_destroy(pl.handle)
+
+
 # ---- 4. beyond fast_ok ----------------------------------------------------------------------------------------------------------
 def test_half_width_12_is_served_beyond_the_sweeps_range_guard(gpu_device):
     from rpgp_amd import ops
