@@ -1,6 +1,9 @@
 // rpgp_f64.hip — float64 variants of the hot-path kernels for `--double` (training_routines.py:481:
 // `type_ = torch.double if double else torch.float`).  Parity path, not a performance path: software exp, plain
-// lane-owns-row tiling (no symmetry / rotation / slabs), every j-piece accumulates into the output in a fixed order.
+// lane-owns-row tiling (no symmetry / rotation / slabs).  The j-pieces and T chunks are launched one after the other on the
+// stream, but inside a launch the column splits ADD their parts to the output with float64 atomics, in whatever order the
+// workgroups arrive: the product and the derivative are not bitwise repeatable (last bits only).  The dense block, the
+// projection and its gradient have one writer per element and are repeatable.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
