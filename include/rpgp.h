@@ -615,6 +615,43 @@ int rpgp_family_generic_bilinear(int dtype, int kind, int group, int ncomp, cons
                                  int64_t lds, double scale, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Full (non-additive) radial kernels, matrix-free (csrc/rpgp_radial.hip): the family's single component of group = d,
+ *     K[i,i'] = scale * phi_kind(|a_i - b_i'|^2),   a, b = rows of Z1 (M x d), Z2 (N x d), already centred and divided by the
+ * lengthscales, `kind` an RPGP_KIND_* value, 1 <= d <= 1024 (the reference's UCI sets reach d = 385).  float32.  The squared
+ * distance is the Gram form d2 = max(|a|^2 + |b|^2 - 2 a.b, 0) with a.b an exact-fp32 FMA chain on v_mfma_f32_16x16x4_f32
+ * (operands staged through LDS in feature chunks; row norms once per launch); phi runs on the VALU.  One writer per output
+ * element, fixed summation order, no atomics: repeated calls are bit-identical.
+ * Numerics (u = 2^-24): |delta d2_ij| <= (d + 4) u (|a_i| + |b_j|)^2 for any summation order, so
+ *     |delta K_ij| <= scale (C_phi (d + 4) u (|a_i| + |b_j|)^2 + c u (1 + d2 |phi'(d2)|)),
+ * C_phi = max |phi'| = 0.5 (RBF), 1.5 (Matern), 0.5 (InverseMQ), pi^2 / 2 (Cosine).  The error grows with the NORMS of the
+ * rows, not with their distance: the caller subtracts one common centre from Z1 and Z2 (the kernel is translation-invariant).
+ * The derivative's a_i r_i - (M A)_i cancels for near-duplicate rows; its relative error in norm is ~3e-7 at lengthscales of
+ * sqrt(d) and up to ~5e-3 where K is close to the identity and the gradient itself is negligible.
+ *   rpgp_radial_mvm            out (M x T) = scale K(Z1, Z2) V; Z2 == NULL: the symmetric operator on Z1 (M == N) with
+ *                              + noise V, d2 forced to 0 on the diagonal so that the diagonal entry is exactly
+ *                              scale phi(0) + noise.  V is N x T, out M x T, both contiguous; T <= 16.  Few rows: the columns
+ *                              are split over workgroups and summed in split order.
+ *   rpgp_radial_dense          out (M x N, leading dimension ldo) = scale K(Z1, Z2); Z1 == Z2 (same pointer, M == N): exact
+ *                              diagonal as above.
+ *   rpgp_radial_bilinear_grad  the convention of rpgp_family_bilinear_grad for one component: gZ[i][m] (N x d, leading
+ *                              dimension ldg) = 2 scale sum_j S_ij phi'(d2_ij) (a_im - a_jm), gscale[0] (DEVICE) = 0.5 sum S o phi
+ *                              (no factor `scale`).  S == NULL: S = L R^T + R L^T from the N x T factors (contiguous, T <= 16);
+ *                              otherwise S is an explicit symmetric N x N matrix with leading dimension lds (L, R, T ignored).
+ * Workspace of all three: rpgp_radial_workspace_bytes(M, N, T) (the derivative: M = N; dense and derivative: any T), 16-byte
+ * aligned; RPGP_EWORKSPACE if smaller.  RPGP_EINVAL: d outside 1 ... 1024, T outside 1 ... 16, an unknown kind, a null or
+ * misaligned pointer, a leading dimension smaller than the row length.
+ */
+size_t rpgp_radial_workspace_bytes(int64_t M, int64_t N, int T);
+int rpgp_radial_mvm(int kind, const float *Z1, const float *Z2, const float *V, float *out, int64_t M, int64_t N, int d,
+                    int ldz1, int ldz2, int T, float scale, float noise, void *workspace, size_t workspace_bytes,
+                    void *stream);
+int rpgp_radial_dense(int kind, const float *Z1, const float *Z2, float *out, int64_t M, int64_t N, int d, int ldz1, int ldz2,
+                      int64_t ldo, float scale, void *workspace, size_t workspace_bytes, void *stream);
+int rpgp_radial_bilinear_grad(int kind, const float *Z, const float *L, const float *R, const float *S, float *gZ,
+                              float *gscale, int64_t N, int d, int ldz, int ldg, int T, int64_t lds, float scale,
+                              void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Native mBCG executor (replaces gpytorch.utils.linear_cg as configured at gp_experiment_runner.py:324-329; algorithm in
  * SURVEY.md Appendix B.2).  Solves (A) X = rhs for T <= 16 right-hand sides with A described by `rpgp_operator`
  * (noise included), optional Woodbury preconditioner M = L L^T + sigma2 I given as L (N x k, k <= 16) and
@@ -639,6 +676,8 @@ int rpgp_family_generic_bilinear(int dtype, int kind, int group, int ncomp, cons
 #define RPGP_OP_LOWRANK_FAMILY 8  /* the same with per-component weights (rpgp_mvm_sym_lowrank_weighted): prep = the plan HANDLE,
                                      family = an RBF, group-1 family with ncomp == J (its device weights); any other family is
                                      RPGP_EINVAL; N, J, j0, j1, scale, noise as for RPGP_OP_LOWRANK; unsharded only */
+#define RPGP_OP_RADIAL 9          /* rpgp_radial_mvm on Z (N x J, leading dimension ldz): J = d input columns, family->kind =
+                                     the RPGP_KIND_* value (group, ncomp, weights unused); scale, noise; unsharded only */
 typedef struct rpgp_operator {
   int kind;
   int64_t N;

@@ -126,6 +126,11 @@ SIGNATURES = {
     "rpgp_family_generic_bilinear_workspace_bytes": (_sz, [_int, _i64, _int]),
     "rpgp_family_generic_bilinear": (_int, [_int, _int, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int,
                                             _i64, _f64, _vp, _sz, _vp]),
+    "rpgp_radial_workspace_bytes": (_sz, [_i64, _i64, _int]),
+    "rpgp_radial_mvm": (_int, [_int, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _f32, _f32, _vp, _sz, _vp]),
+    "rpgp_radial_dense": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _i64, _f32, _vp, _sz, _vp]),
+    "rpgp_radial_bilinear_grad": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _i64, _f32, _vp, _sz,
+                                         _vp]),
     "rpgp_ski_bilinear_grad_comp": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _f32, _vp,
                                            _sz, _vp, _vp]),
     "rpgp_mbcg_workspace_bytes": (_sz, [_vp, _int, _int]),
@@ -202,6 +207,7 @@ RPGP_OP_FUSED, RPGP_OP_FUSED_PREPARED, RPGP_OP_SKI, RPGP_OP_DENSE, RPGP_OP_FAMIL
 RPGP_OP_SUM = 6
 RPGP_OP_LOWRANK = 7
 RPGP_OP_LOWRANK_FAMILY = 8
+RPGP_OP_RADIAL = 9
 RPGP_LOWRANK_GRAD_BYTES = 65536
 RPGP_KIND_RBF, RPGP_KIND_MATERN15, RPGP_KIND_IMQ, RPGP_KIND_COSINE = 0, 1, 2, 3
 RPGP_KIND_PRODUCT = 16

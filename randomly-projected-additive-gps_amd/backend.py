@@ -54,6 +54,12 @@ class HipBackend:
     family_bilinear_grad = staticmethod(ops.family_bilinear_grad)
     family_bilinear_grad_dense = staticmethod(ops.family_bilinear_grad_dense)
     family_pivoted_cholesky = staticmethod(ops.family_pivoted_cholesky)
+    make_radial_family = staticmethod(ops.RadialFamily)
+    radial_mvm = staticmethod(ops.radial_mvm)
+    radial_dense = staticmethod(ops.radial_dense)
+    radial_bilinear_grad = staticmethod(ops.radial_bilinear_grad)
+    radial_bilinear_grad_dense = staticmethod(ops.radial_bilinear_grad_dense)
+    radial_max_dims = ops.RADIAL_MAX_DIMS
     gram_f64 = staticmethod(ops.gram_f64)
     woodbury_apply = staticmethod(ops.woodbury_apply)
     woodbury_setup = staticmethod(ops.woodbury_setup)

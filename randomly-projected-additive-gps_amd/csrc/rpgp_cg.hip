@@ -954,6 +954,12 @@ int apply_operator(const rpgp_operator *op, const ShardCtx &sh, const float *V, 
     case RPGP_OP_FAMILY:
       rc = rpgp_family_mvm_sym(op->family, op->Z, V, out, op->N, op->ldz, T, op->scale, noise, ws, ws_bytes, stream);
       break;
+    case RPGP_OP_RADIAL:
+      // (unsharded only; the kind of the full radial kernel rides in family->kind, J = the d input columns)
+      if (partial || world != 1 || !op->family) return RPGP_EINVAL;
+      rc = rpgp_radial_mvm(op->family->kind, op->Z, nullptr, V, out, op->N, op->N, op->J, op->ldz, op->ldz, T, op->scale,
+                           op->noise, ws, ws_bytes, stream);
+      break;
     default:
       return RPGP_EINVAL;
   }
@@ -979,6 +985,8 @@ size_t operator_workspace(const rpgp_operator *op, int T) {
       return rpgp_symcache_workspace_bytes(op->N, T, world, rank);
     case RPGP_OP_FAMILY:
       return rpgp_family_mvm_workspace_bytes(op->N, op->N, T, 1);
+    case RPGP_OP_RADIAL:
+      return rpgp_radial_workspace_bytes(op->N, op->N, T);
     case RPGP_OP_SUM: {
       const rpgp_operator *parts = reinterpret_cast<const rpgp_operator *>(op->prep);
       size_t mx = 0;

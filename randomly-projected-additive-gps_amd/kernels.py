@@ -12,8 +12,8 @@ from torch.nn import functional as F
 
 from . import backend as _backend
 from .distributed import JShard, RowShard
-from .operators import (AdditiveRPOperator, FamilyAdditiveOperator, MixedGroupOperator, SKIAdditiveOperator,
-                        padded_group_size)
+from .operators import (AdditiveRPOperator, FamilyAdditiveOperator, FullKernelOperator, MixedGroupOperator,
+                        SKIAdditiveOperator, padded_group_size)
 
 
 def inv_softplus(y):
@@ -456,6 +456,47 @@ class RBFKernel(Kernel):
             return (1.0 + math.sqrt(3.0) * r) * torch.exp(-math.sqrt(3.0) * r)
         return torch.cos(math.pi * r)
 
+    # why the radial kernels did not serve the last forward() — "settings.fused_full is off" included; None once a forward() was
+    # served (and before the first call)
+    fused_full_reason = None
+
+    def _fused_full_reason(self, x1, x2):
+        """None when the radial kernels serve K(x1, x2) under settings.fused_full, else why they do not."""
+        from . import settings
+        if settings.fused_full.off():
+            return "settings.fused_full is off"
+        be = _backend.get_backend()
+        if not all(hasattr(be, n) for n in ("radial_mvm", "radial_dense", "radial_bilinear_grad", "radial_bilinear_grad_dense")):
+            return "the backend has no radial entries"
+        if x1.dtype != torch.float32 or x2.dtype != torch.float32 or self.raw_lengthscale.dtype != torch.float32:
+            return "float64 inputs (--double): the radial kernels are float32"
+        if getattr(be, "name", "") == "hip-gfx950" and not (x1.is_cuda and x2.is_cuda):
+            return "host tensors: the radial kernels run on the device"
+        if x1.dim() != 2 or x2.dim() != 2 or x1.shape[1] != x2.shape[1]:
+            return "inputs are not two N x d matrices"
+        if x1.shape[1] > getattr(be, "radial_max_dims", 1024):
+            return "d = %d is above the %d columns the radial kernels take" % (x1.shape[1], getattr(be, "radial_max_dims", 1024))
+        from .distributed import is_distributed
+        if is_distributed():
+            return "a process group of more than one rank: the radial operator is not sharded"
+        return None
+
     def forward(self, x1, x2, outputscale=None, **params):
+        self.fused_full_reason = reason = self._fused_full_reason(x1, x2)
+        if reason is None:
+            # Z = (x - mu) / lengthscale inside autograd (the lengthscale gradient, ARD or single, comes from gZ by the chain
+            # rule).  mu: the column mean of the training inputs, detached, once per model — the kernel is translation-
+            # invariant, and the Gram form's rounding error grows with (|a| + |b|)^2, not with |a - b|^2 (DESIGN.md 7.10).
+            # The first call of a model is on its training inputs (the prior in training, the strategy's caches in evaluation);
+            # mu is fixed at that first served call whatever it is, so a kernel first called on other data keeps THAT mean: K is
+            # the same function by translation invariance, only the error bound is then that of rows not centred at zero.
+            mu = getattr(self, "_center", None)
+            if mu is None or mu.shape[0] != x2.shape[1] or mu.device != x2.device or mu.dtype != x2.dtype:
+                mu = self._center = x2.detach().mean(dim=0)
+            same = x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+            ls = self.lengthscale
+            z1 = (x1 - mu) / ls
+            z2 = None if same else (x2 - mu) / ls
+            return FullKernelOperator(z1, z2, outputscale=outputscale, kind=self.kernel_type)
         from .dense_ops import DenseKernelOperator
         return DenseKernelOperator(self, x1, x2, outputscale)

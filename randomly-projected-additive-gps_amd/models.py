@@ -108,7 +108,7 @@ class PredictionStrategy:
                 shard = getattr(self.op, "shard", None)
                 sharded = shard is not None and shard.world_size > 1
                 cacheable = isinstance(self.op, AdditiveRPOperator) and not isinstance(self.op, SKIAdditiveOperator) and \
-                    x.dtype == torch.float32
+                    x.dtype == torch.float32 and getattr(self.op, "cacheable", True)
                 per_rank = 2.0 / (shard.world_size if sharded else 1)     # pair-sharded ranks cache their own share
                 cache = self.op.to_symcache() if cacheable and settings.use_cached_kernel(N, x.device, per_rank) else None
                 if cache is not None:

@@ -979,8 +979,160 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         return self._finish_grads(gZ, gc)
 
 
+class FullKernelOperator(AdditiveRPOperator):
+    """K = outputscale * phi_kind(|z_i - z_i'|^2) over ALL d columns of Z — the `full` kinds (training_routines.py:275-293: one
+    RBF / Matern / InverseMQ / Cosine kernel on all inputs, ARD or not) matrix-free (settings.fused_full): the family's single
+    component of group = d on the radial kernels (csrc/rpgp_radial.hip), whose squared distance is a Gram product on the fp32
+    matrix cores, for any d <= 1024.  Z is already CENTRED (the Gram form's rounding error grows with the norms of the rows,
+    not with their distance) and divided by the lengthscales, both inside autograd, so that the lengthscale gradient comes
+    from gZ by the chain rule.  Same protocol as the additive operators: the marginal likelihood and the prediction strategy
+    take their CG / SLQ / pivoted-Cholesky / LOVE routes.  Unsharded, float32, never cached as an N x N matrix."""
+
+    cacheable = False              # (solve_operator / PredictionStrategy: no dense or packed copy of K; the product is the point)
+
+    def __init__(self, Z1, Z2=None, outputscale=None, kind="RBF"):
+        super().__init__(Z1, Z2, outputscale, 1.0, shard=None)
+        self.kind = kind
+        self._fam = None
+        self._route = None          # None undecided, False the radial kernels, else (family, padded Z1, padded Z2 or None)
+
+    def _family_route(self):
+        """The RBF with d <= 20 columns as ONE component of group d of the family tile kernels (zero columns up to the next
+        instantiated group size): (family, padded Z1, padded Z2 or None) for the backend's family_* entries, or None for the
+        radial kernels.  Measured on the MI355X at N = 50 000: the tile kernel takes 0.8 / 1.4 ms (T = 1) and
+        2.1 / 2.7 ms (T = 11) at d = 8 / 20 against 4.0 - 4.7 ms of the radial kernel, far beyond the 5 % spread; the other kinds
+        have no tile kernel for a radial group, and d > 20 none at all.  The entries are called directly (no
+        FamilyAdditiveOperator in between: no low-rank decision of its own, no host read of the weight); `_FULL_FAMILY_ROUTE`
+        (private: tools/radial_bench.py times both) switches the route off."""
+        if self._route is None:
+            be = _backend.get_backend()
+            d = self.Z1.shape[1]
+            names = ("make_family", "family_mvm_sym", "family_mvm_rect", "family_dense", "family_bilinear_grad",
+                     "family_bilinear_grad_dense")
+            if not _FULL_FAMILY_ROUTE or self.kind != "RBF" or d > _FAMILY_GROUPS[-1] or self.Z1.dtype != torch.float32 or \
+                    not all(hasattr(be, n) for n in names):
+                self._route = False
+            else:
+                g = padded_group_size(d)
+
+                def pad(Z):
+                    return None if Z is None else torch.nn.functional.pad(Z.detach(), (0, g - d)).contiguous()
+                fam = be.make_family("RBF", g, torch.ones(1, dtype=torch.float32, device=self.Z1.device))
+                self._route = False if getattr(fam, "generic", False) else (fam, pad(self.Z1), pad(self.Z2))
+        return self._route or None
+
+    def lowrank_form(self, noise=None):
+        return None
+
+    def lowrank_mll_form(self, noise=None):
+        self._lowrank_mll = (None, "the full kernel has no low-rank feature form")
+        return None
+
+    def fused_pivoted_cholesky(self, rank):
+        return None                # (the torch loop over _get_rows builds the preconditioner)
+
+    def to_symcache(self, wide=False):
+        return None
+
+    def _local_matmul(self, rhs, noise=0.0):
+        route = self._family_route()
+        be = _backend.get_backend()
+        if route is not None:
+            fam, z1, z2 = route
+            if self.symmetric:
+                return be.family_mvm_sym(fam, z1, rhs, self._scale, noise)
+            return be.family_mvm_rect(fam, z1, z2, rhs, self._scale)
+        return be.radial_mvm(self.kind, self.Z1.detach(), None if self.symmetric else self.Z2.detach(), rhs, self._scale,
+                             noise if self.symmetric else 0.0)
+
+    def _matmul(self, rhs, noise=0.0):
+        if noise and not self.symmetric:
+            raise ValueError("a diagonal can only be added to the square symmetric operator")
+        return self._local_matmul(rhs.detach(), noise)
+
+    def native_descriptor(self, noise=0.0):
+        be = _backend.get_backend()
+        route = self._family_route()
+        if not self.symmetric or not hasattr(be, "mbcg_solve"):
+            return None
+        from . import _lib
+        if route is not None:
+            fam, z1, _ = route
+            return be.make_operator_desc(_lib.RPGP_OP_FAMILY, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1, family=fam)
+        if not hasattr(be, "make_radial_family"):
+            return None
+        if self._fam is None:
+            self._fam = be.make_radial_family(self.kind, self.Z1.shape[1])
+        z1 = self.Z1.detach().contiguous()
+        return be.make_operator_desc(_lib.RPGP_OP_RADIAL, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1, family=self._fam)
+
+    def native_sharding(self):
+        return None
+
+    def _transpose_nonbatch(self):
+        if self.symmetric:
+            return self
+        return FullKernelOperator(self.Z2, self.Z1, self.outputscale, self.kind)
+
+    def _diagonal(self):
+        if not self.symmetric:
+            raise RuntimeError("diagonal of a rectangular cross-covariance requested")
+        # phi(0) = 1 for every member, and the symmetric product forces d2 = 0 on the diagonal: k(x, x) = outputscale exactly
+        return torch.full((self.Z1.shape[0],), self._scale, dtype=self.dtype, device=self.device)
+
+    def _get_rows(self, idx):
+        route = self._family_route()
+        be = _backend.get_backend()
+        if route is not None:
+            fam, z1, z2 = route
+            return be.family_dense(fam, z1.index_select(0, idx).contiguous(), z1 if self.symmetric else z2, self._scale)
+        z2 = self.Z1 if self.symmetric else self.Z2
+        rows = be.radial_dense(self.kind, self.Z1.detach().index_select(0, idx).contiguous(), z2.detach(), self._scale)
+        if self.symmetric:
+            # the selected rows are a copy, so the kernel cannot know which entries are diagonal ones: they get the value
+            # _diagonal() claims, scale * phi(0), exactly as in the product and the square dense block
+            rows[torch.arange(idx.numel(), device=rows.device), idx] = self._scale
+        return rows
+
+    def to_dense(self):
+        route = self._family_route()
+        be = _backend.get_backend()
+        if route is not None:
+            fam, z1, z2 = route
+            return be.family_dense(fam, z1, z1 if self.symmetric else z2, self._scale)
+        z1 = self.Z1.detach().contiguous()
+        return be.radial_dense(self.kind, z1, z1 if self.symmetric else self.Z2.detach(), self._scale)
+
+    evaluate = to_dense
+
+    def to_dense_cached(self):
+        return self.to_dense()
+
+    def _bilinear_derivative(self, left_vecs, right_vecs):
+        if not self.symmetric:
+            raise NotImplementedError("derivatives are only needed for the train-train kernel")
+        route = self._family_route()
+        if route is not None:
+            gZ, gc = _backend.get_backend().family_bilinear_grad(route[0], route[1], left_vecs.detach(), right_vecs.detach(),
+                                                                 self._scale)
+            return gZ[:, :self.Z1.shape[1]].contiguous(), gc.reshape(-1)[0]
+        return _backend.get_backend().radial_bilinear_grad(self.kind, self.Z1.detach(), left_vecs.detach(),
+                                                           right_vecs.detach(), self._scale)
+
+    _quad_form_derivative = _bilinear_derivative
+
+    def dense_weight_derivative(self, S):
+        route = self._family_route()
+        if route is not None:
+            gZ, gc = _backend.get_backend().family_bilinear_grad_dense(route[0], route[1], S, self._scale)
+            return gZ[:, :self.Z1.shape[1]].contiguous(), gc.reshape(-1)[0]
+        return _backend.get_backend().radial_bilinear_grad_dense(self.kind, self.Z1.detach(), S, self._scale)
+
+
 # group sizes the family tile kernels are instantiated for (ops.FAMILY_GROUPS); other sizes are padded with zero columns
 _FAMILY_GROUPS = (1, 2, 3, 4, 5, 8, 10, 20)
+# FullKernelOperator._family_route (private: False keeps every full kernel on the radial kernels, for measurements)
+_FULL_FAMILY_ROUTE = True
 
 
 def padded_group_size(k):

@@ -1619,6 +1619,115 @@ def family_bilinear_grad_dense(fam, Z, S, scale):
     return gZ, gc
 
 
+# ------------------------------------------------------------------------------------ full radial kernels
+
+RADIAL_MAX_DIMS = 1024
+
+
+class RadialFamily:
+    """The `struct rpgp_family` of an RPGP_OP_RADIAL descriptor: only `kind` is read (group = d, one component, no weights)."""
+
+    def __init__(self, kind, d):
+        self.kind = KINDS[kind] if isinstance(kind, str) else int(kind)
+        self.struct = _lib.RpgpFamily(self.kind, int(d), 1, None)
+
+
+def _radial_kind(kind):
+    return KINDS[kind] if isinstance(kind, str) else int(kind)
+
+
+def radial_mvm(kind, Z1, Z2, V, scale, noise=0.0):
+    """out (M x T) = scale * phi_kind(|a_i - b_j|^2) @ V over ALL columns of Z1, Z2 (rpgp_radial_mvm); Z2 None: the symmetric
+    operator on Z1 with + noise * V and an exact diagonal.  Blocks wider than 16 columns go through in 16-column pieces."""
+    lib = _lib.load()
+    Z1 = _require(Z1, "Z1", 2)
+    Z2 = None if Z2 is None else _require(Z2, "Z2", 2)
+    M, d = Z1.shape
+    N = M if Z2 is None else Z2.shape[0]
+    if Z2 is not None and Z2.shape[1] != d:
+        raise ValueError("Z1 and Z2 must have the same number of columns")
+    V2, squeeze = _as_matrix(V, N, "V")
+    T = V2.shape[1]
+    out = torch.empty((M, T), dtype=torch.float32, device=Z1.device)
+    k = _radial_kind(kind)
+    with _on(Z1.device):
+        ws = _workspace(Z1.device, lib.rpgp_radial_workspace_bytes(M, N, min(T, 16)))
+        for t0 in range(0, max(T, 1), 16):
+            whole = T <= 16
+            Vc = V2 if whole else V2[:, t0:t0 + 16].contiguous()
+            oc = out if whole else torch.empty((M, Vc.shape[1]), dtype=torch.float32, device=Z1.device)
+            _lib.check(lib.rpgp_radial_mvm(k, Z1.data_ptr(), None if Z2 is None else Z2.data_ptr(), Vc.data_ptr(),
+                                           oc.data_ptr(), M, N, d, d, d, Vc.shape[1], float(scale), float(noise),
+                                           ws.data_ptr(), ws.numel(), _stream()), "rpgp_radial_mvm")
+            if not whole:
+                out[:, t0:t0 + 16] = oc
+    return out.squeeze(1) if squeeze else out
+
+
+def radial_dense(kind, Z1, Z2, scale):
+    """Dense block scale * phi_kind(|a_i - b_j|^2) (M x N) (rpgp_radial_dense); the same memory twice: exact diagonal."""
+    lib = _lib.load()
+    Z1 = _require(Z1, "Z1", 2)
+    Z2 = _require(Z2, "Z2", 2)
+    M, d = Z1.shape
+    N = Z2.shape[0]
+    if Z2.shape[1] != d:
+        raise ValueError("Z1 and Z2 must have the same number of columns")
+    out = torch.empty((M, N), dtype=torch.float32, device=Z1.device)
+    with _on(Z1.device):
+        ws = _workspace(Z1.device, lib.rpgp_radial_workspace_bytes(M, N, 0))
+        _lib.check(lib.rpgp_radial_dense(_radial_kind(kind), Z1.data_ptr(), Z2.data_ptr(), out.data_ptr(), M, N, d, d, d, N,
+                                         float(scale), ws.data_ptr(), ws.numel(), _stream()), "rpgp_radial_dense")
+    return out
+
+
+def radial_bilinear_grad(kind, Z, L, R, scale):
+    """(gZ [N x d], gscale []) for sum((L R^T) * K) of the full radial kernel: gscale = 0.5 sum S o phi, S = L R^T + R L^T."""
+    lib = _lib.load()
+    Z = _require(Z, "Z", 2)
+    N, d = Z.shape
+    L2, _ = _as_matrix(L, N, "L")
+    R2, _ = _as_matrix(R, N, "R")
+    if L2.shape != R2.shape:
+        raise ValueError("L and R must have the same shape")
+    T = L2.shape[1]
+    gZ = torch.empty((N, d), dtype=torch.float32, device=Z.device)
+    gs = torch.empty(1, dtype=torch.float32, device=Z.device)
+    k = _radial_kind(kind)
+    with _on(Z.device):
+        ws = _workspace(Z.device, lib.rpgp_radial_workspace_bytes(N, N, 0))
+        gZp, gsp = (None, None) if T <= 16 else (torch.empty_like(gZ), torch.empty_like(gs))
+        for t0 in range(0, max(T, 1), 16):      # the derivative is additive over the columns of L, R
+            first = t0 == 0
+            Lc, Rc = (L2, R2) if T <= 16 else (L2[:, t0:t0 + 16].contiguous(), R2[:, t0:t0 + 16].contiguous())
+            _lib.check(lib.rpgp_radial_bilinear_grad(k, Z.data_ptr(), Lc.data_ptr(), Rc.data_ptr(), None,
+                                                     (gZ if first else gZp).data_ptr(), (gs if first else gsp).data_ptr(), N,
+                                                     d, d, d, Lc.shape[1], 0, float(scale), ws.data_ptr(), ws.numel(),
+                                                     _stream()), "rpgp_radial_bilinear_grad")
+            if not first:
+                gZ += gZp
+                gs += gsp
+    return gZ, gs.reshape(())
+
+
+def radial_bilinear_grad_dense(kind, Z, S, scale):
+    """(gZ, gscale) for 0.5 * sum(S * K) with an explicit symmetric N x N weight matrix S."""
+    lib = _lib.load()
+    Z = _require(Z, "Z", 2)
+    N, d = Z.shape
+    if S.shape != (N, N):
+        raise ValueError("S must be %d x %d" % (N, N))
+    S = _require(S, "S", 2)
+    gZ = torch.empty((N, d), dtype=torch.float32, device=Z.device)
+    gs = torch.empty(1, dtype=torch.float32, device=Z.device)
+    with _on(Z.device):
+        ws = _workspace(Z.device, lib.rpgp_radial_workspace_bytes(N, N, 0))
+        _lib.check(lib.rpgp_radial_bilinear_grad(_radial_kind(kind), Z.data_ptr(), None, None, S.data_ptr(), gZ.data_ptr(),
+                                                 gs.data_ptr(), N, d, d, d, 0, N, float(scale), ws.data_ptr(), ws.numel(),
+                                                 _stream()), "rpgp_radial_bilinear_grad")
+    return gZ, gs.reshape(())
+
+
 def make_operator_desc(kind, N, J, scale, noise, Z=None, prep=None, gp=None, j0=0, j1=None, G=0, Kd=None, family=None,
                        symcache=None, world=1, rank=0, lowrank=None):
     """Fill a `struct rpgp_operator`; returns (struct, keepalive) — keep both referenced while the solve runs.

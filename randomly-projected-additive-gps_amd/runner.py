@@ -257,6 +257,9 @@ def build_parser():
                    help="(rpgp) largest Chebyshev rank served by --lowrank_kernel / --lowrank_posterior / --lowrank_mll (1 ... 128, default 64)")
     p.add_argument("--lowrank_panels", action="store_true",
                    help="(rpgp) with --lowrank_kernel: serve half-widths beyond the rank cap (up to about 100) through the panel plan")
+    p.add_argument("--fused_full", action="store_true",
+                   help="(rpgp) run the `full` kinds (RBF / ARD / InverseMQ on all d inputs) matrix-free through the radial "
+                        "HIP kernels (CG / SLQ / preconditioner) instead of the dense torch path, where served")
     return p
 
 
@@ -412,7 +415,8 @@ def main(argv=None, rank_entry=None):
                 settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)), \
                 settings.lowrank_mll(getattr(args, "lowrank_mll", False)), \
                 settings.lowrank_max_rank(getattr(args, "lowrank_max_rank", 64)), \
-                settings.lowrank_panels(getattr(args, "lowrank_panels", False)):
+                settings.lowrank_panels(getattr(args, "lowrank_panels", False)), \
+                settings.fused_full(getattr(args, "fused_full", False)):
             if args.ablation:
                 if args.k is not None:
                     abl_vars = args.k

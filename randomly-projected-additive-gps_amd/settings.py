@@ -148,6 +148,13 @@ lowrank_kernel = _setting("lowrank_kernel", False, flag=True)
 # prepared coordinates are finite (the sweep's range guard does not bind it), plain and weighted operators alike, the solve and
 # the derivative on the same panels.  Off (the default): every path is the one above, bit for bit.  DESIGN.md 7.9.
 lowrank_panels = _setting("lowrank_panels", False, flag=True)
+# the `full` kinds (one RBF / Matern / InverseMQ / Cosine kernel on all d inputs, ARD or not) matrix-free: kernels.RBFKernel then
+# returns an operators.FullKernelOperator on the radial HIP kernels (csrc/rpgp_radial.hip: the squared distance as a Gram product
+# on the fp32 matrix cores) and the model takes the CG / SLQ / pivoted-Cholesky / LOVE routes of the additive operators — no
+# N x N object above the Cholesky size.  Served: float32 inputs on the device, d <= 1024, one rank, a backend with the radial
+# entries; anything else keeps the dense torch operator (RBFKernel.fused_full_reason says why).  Off (the default): every path
+# is the dense one, bit for bit.  DESIGN.md 7.10.
+fused_full = _setting("fused_full", False, flag=True)
 # prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
 # with a float64 twin (k = 1, no grid), J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default, up to 128), at most 4096
 # features in 25 % of the device memory gets its posterior mean, covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or
