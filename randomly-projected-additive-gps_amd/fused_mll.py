@@ -254,8 +254,7 @@ class _FusedMLL(torch.autograd.Function):
             sign = ctx.sign
             left, right, part, nparts = be.step_lr(ctx.solves, pre_probes, g, sign * -0.5 / n)
             op, gs_scale = ctx.op, 1.0
-            from .operators import AdditiveRPOperator
-            if type(op) is AdditiveRPOperator and (op.shard is None or op.shard.world_size <= 1):
+            if op.plain_unsharded:
                 # (the plain operator's `_bilinear_derivative` is this call followed by `gs * weight`: the weight rides into the
                 #  chain-rule kernel instead of being one more launch)
                 lr = op.lowrank_form() if op.lowrank_served else None     # (the solve decided the form of this step)

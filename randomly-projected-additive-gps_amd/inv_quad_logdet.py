@@ -14,7 +14,7 @@ import torch
 from . import settings
 from .hostvals import host_float, peek
 from .linear_cg import linear_cg
-from .operators import AddedDiagOperator, DenseOperator, SKIAdditiveOperator, SymCachedOperator
+from .operators import AddedDiagOperator, DenseOperator, SymCachedOperator
 from .precond import build_preconditioner
 
 
@@ -90,7 +90,7 @@ def solve_operator(op, khat, Z, noise_f, width):
     if settings.lowrank_kernel.on() and getattr(op, "lowrank_form", None) is not None and \
             op.lowrank_form(noise_f) is not None:
         return matmul, native_op, sharded          # the low-rank form (RPGP_OP_LOWRANK): no cache to build
-    if not isinstance(op, SKIAdditiveOperator) and Z.dtype == torch.float32 and getattr(op, "cacheable", True):
+    if op.kernel_copy_ok:
         per_rank = 2.0 / (op.shard.world_size if sharded else 1)
         cache = op.to_symcache(wide=width > 4) if hasattr(op, "to_symcache") and \
             settings.use_cached_kernel(N, Z.device, per_rank) else None

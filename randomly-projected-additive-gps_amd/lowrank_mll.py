@@ -72,10 +72,7 @@ class ColumnFeatureForm:
 
 def _served_kind(op):
     """None when `op` is of a kind the features mode serves, else the reason."""
-    from .operators import AdditiveRPOperator, FamilyAdditiveOperator
-    plain = type(op) is AdditiveRPOperator
-    weighted = type(op) is FamilyAdditiveOperator and op.kind == "RBF" and op.group == 1 and not op.product
-    if not (plain or weighted) or not op.symmetric:
+    if op.feature_form_kind is None:
         return "not a plain symmetric additive-RP RBF operator (grid, family, k > 1 or rectangular)"
     return None
 
@@ -130,7 +127,7 @@ def _decide(op, noise):
     why = _served_kind(op)
     if why:
         return None, why
-    weighted = getattr(op, "comp_weights", None) is not None
+    weighted = op.feature_form_kind == "weighted"
     if getattr(op, "memory_efficient", False) or settings.memory_efficient.on():
         return None, "memory-efficient kernel"
     if (op.shard is not None and getattr(op.shard, "world_size", 1) > 1) or getattr(op, "row_shard", None) is not None:

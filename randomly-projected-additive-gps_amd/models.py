@@ -107,8 +107,7 @@ class PredictionStrategy:
                 self.chol = None
                 shard = getattr(self.op, "shard", None)
                 sharded = shard is not None and shard.world_size > 1
-                cacheable = isinstance(self.op, AdditiveRPOperator) and not isinstance(self.op, SKIAdditiveOperator) and \
-                    x.dtype == torch.float32 and getattr(self.op, "cacheable", True)
+                cacheable = getattr(self.op, "kernel_copy_ok", False)
                 per_rank = 2.0 / (shard.world_size if sharded else 1)     # pair-sharded ranks cache their own share
                 cache = self.op.to_symcache() if cacheable and settings.use_cached_kernel(N, x.device, per_rank) else None
                 if cache is not None:
@@ -347,7 +346,7 @@ class PredictionStrategy:
             # at N = 50k, T = 2000; 115 vs 45 ms at N = T = 14 939), so it is densified only below that.
             N = B.shape[0]
             fits = (4.0 * N * N <= 0.25 * torch.cuda.get_device_properties(B.device).total_memory) if B.is_cuda else True
-            if isinstance(self.op, SKIAdditiveOperator) and N > 32768:
+            if not self.op.densify_for_wide_solve(N):
                 fits = False
             if fits:
                 if getattr(self, "_dense_khat", None) is None:
@@ -390,7 +389,7 @@ class PredictionStrategy:
         N = self.r.shape[0]
         if self.dense_path or not isinstance(self.op, AdditiveRPOperator) or N > settings.dense_solve_size.value():
             return None
-        if isinstance(self.op, SKIAdditiveOperator) and N > 32768:
+        if not self.op.densify_for_wide_solve(N):
             return None
         if like.is_cuda and 4.0 * N * N > 0.25 * torch.cuda.get_device_properties(like.device).total_memory:
             return None

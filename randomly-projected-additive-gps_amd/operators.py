@@ -5,12 +5,28 @@ Method names follow GPyTorch's LazyTensor / `linear_operator.LinearOperator` pro
 `representation`) so the solver stack (linear_cg, pivoted Cholesky, prediction strategy) reads like the
 reference's dependency.  All arithmetic goes through the compute backend (HIP library); K is never stored unless
 `to_dense()` / the cached mode is requested.
+
+`AdditiveRPOperator` writes the protocol once; the other kernel families override its hooks.
 """
 import torch
 
 from . import backend as _backend
 from .hostvals import host_float
 from . import settings
+# group sizes the family tile kernels are instantiated for; other sizes are padded with zero columns
+from .ops import FAMILY_GROUPS as _FAMILY_GROUPS
+
+# FullKernelOperator._family_route (private: False keeps every full kernel on the radial kernels, for measurements)
+_FULL_FAMILY_ROUTE = True
+
+
+def padded_group_size(k):
+    """Smallest instantiated group size >= k (an RBF group padded with all-zero coordinates is the same kernel:
+    exp(-0.5 sum d^2) gains factors exp(0))."""
+    for g in _FAMILY_GROUPS:
+        if g >= k:
+            return g
+    raise NotImplementedError("multiplicative groups of more than %d dimensions are not built" % _FAMILY_GROUPS[-1])
 
 
 def _plan_keywords(plan_fn):
@@ -31,6 +47,11 @@ def _plan_keywords(plan_fn):
         if "panels" in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values()):
             kw["panels"] = True
     return kw
+
+
+def _rows(Z, idx):
+    """The left operand of a dense block: all rows of Z (to_dense), or a contiguous copy of the rows `idx` (_get_rows)."""
+    return Z if idx is None else Z.index_select(0, idx).contiguous()
 
 
 class LinearOperator:
@@ -86,7 +107,8 @@ class LinearOperator:
     def to_dense(self):
         raise NotImplementedError
 
-    evaluate = to_dense
+    def evaluate(self):
+        return self.to_dense()
 
     def representation(self):
         raise NotImplementedError
@@ -95,7 +117,8 @@ class LinearOperator:
         """Gradients of sum((left right^T) * self) w.r.t. each tensor of `representation()`."""
         raise NotImplementedError
 
-    _quad_form_derivative = _bilinear_derivative
+    def _quad_form_derivative(self, left_vecs, right_vecs):
+        return self._bilinear_derivative(left_vecs, right_vecs)
 
     def add_diag(self, diag_value):
         return AddedDiagOperator(self, diag_value)
@@ -109,7 +132,17 @@ class AdditiveRPOperator(LinearOperator):
     Z1, Z2: projected inputs (N x J), produced by `ScaledProjectionKernel` (scaled_projection_kernel.py:21-37).
     `Z2 is None` means the symmetric train-train kernel: each unordered pair is evaluated once.
     `shard` (rpgp_amd.distributed.JShard) splits the J terms across ranks with one all-reduce per MVM.
+
+    Also the skeleton of the protocol for every kernel family: the guards, the detach, the transpose of a
+    symmetric operator, `_get_rows` / `to_dense` and `representation` are written here once, over the hooks `_local_matmul`,
+    `_diagonal_value`, `_dense_block`, `_swapped` and `_bilinear_grads` (and, where a family has them, `native_descriptor`,
+    `fused_pivoted_cholesky`, `lowrank_form`, `dense_weight_derivative`).
     """
+
+    plain = True               # this class's own kernel: False on every other family, which has none of its fast paths (the fused
+    #                            pivoted Cholesky, the padded dense block, the packed symmetric cache, the Chebyshev plan)
+    cacheable = True           # a dense or packed copy of K may be built for the solves (kernel_copy_ok: and float32)
+    comp_weights = None        # per-component output scales: the families that have them add them to representation()
 
     def __init__(self, Z1, Z2=None, outputscale=None, weight=1.0, shard=None):
         self.Z1 = Z1
@@ -136,6 +169,30 @@ class AdditiveRPOperator(LinearOperator):
     @_scale.setter
     def _scale(self, value):
         self._scale_value = float(value)
+
+    # ---- what the call sites ask instead of the operator's class ---------------------------------------------------
+    @property
+    def _sharded(self):
+        return self.shard is not None and self.shard.world_size > 1
+
+    @property
+    def kernel_copy_ok(self):
+        """Whether a dense or packed copy of K may be built for the solves (cached-K mode)."""
+        return self.cacheable and self.dtype == torch.float32
+
+    def densify_for_wide_solve(self, n):
+        """Whether a solve with many right-hand sides may run on the dense matrix at n rows."""
+        return True
+
+    @property
+    def plain_unsharded(self):
+        """The plain operator on one rank: its derivative is the backend's bilinear_grad and one factor `weight`."""
+        return self.plain and not self._sharded
+
+    @property
+    def feature_form_kind(self):
+        """Which feature form lowrank_mll.decide may serve this operator with: "plain", "weighted" or None."""
+        return "plain" if self.plain and self.symmetric else None
 
     # ---- protocol -------------------------------------------------------------------------------------------
     def _size(self):
@@ -165,7 +222,7 @@ class AdditiveRPOperator(LinearOperator):
         z1 = self.Z1.detach()
         if self.symmetric:
             kw = {}
-            if self.shard is not None and self.shard.world_size > 1:
+            if self._sharded:
                 ps = self.shard.pair_shard(be)
                 if ps is not None and z1.dtype == torch.float32:    # pair-sharding: all projections, 1/world of the pairs
                     j0, j1 = 0, self.num_projections
@@ -182,23 +239,19 @@ class AdditiveRPOperator(LinearOperator):
         return be.mvm_rect(z1, self.Z2.detach(), rhs, self._scale, j0=j0, j1=j1)
 
     def _matmul(self, rhs, noise=0.0):
-        rhs = rhs.detach()
-        if self.shard is None or self.shard.world_size == 1:
-            out = self._local_matmul(rhs, noise if self.symmetric else 0.0)
-            if noise and not self.symmetric:
-                raise ValueError("a diagonal can only be added to the square symmetric operator")
-            return out
         if noise and not self.symmetric:
             raise ValueError("a diagonal can only be added to the square symmetric operator")
-        return self.shard.sharded_mvm(lambda j0, j1, nz: self._local_matmul(rhs, nz), rhs, float(noise))
+        rhs = rhs.detach()
+        if self._sharded:
+            return self.shard.sharded_mvm(lambda j0, j1, nz: self._local_matmul(rhs, nz), rhs, float(noise))
+        return self._local_matmul(rhs, noise if self.symmetric else 0.0)
 
     def fused_pivoted_cholesky(self, rank):
         """Single-launch pivoted Cholesky (rpgp_pivoted_cholesky) when the backend has it and the kernel is not sharded;
         None otherwise (callers fall back to the generic row-by-row version)."""
         be = _backend.get_backend()
-        if type(self) is not AdditiveRPOperator or not self.symmetric or not hasattr(be, "pivoted_cholesky") or \
-                self.Z1.dtype != torch.float32 or \
-                (self.shard is not None and self.shard.world_size > 1) or self.num_projections > 64 or rank > 64:
+        if not self.plain_unsharded or not self.symmetric or not hasattr(be, "pivoted_cholesky") or \
+                self.Z1.dtype != torch.float32 or self.num_projections > 64 or rank > 64:
             return None
         return be.pivoted_cholesky(self.Z1.detach().contiguous(), self._scale, min(rank, self.Z1.shape[0]))
 
@@ -208,16 +261,15 @@ class AdditiveRPOperator(LinearOperator):
         N, the scale and the noise (default: the host value the marginal likelihood recorded), so that the solve and the
         derivative of a step use the same form.  Ranks p, q up to settings.lowrank_max_rank (64 by default; above it a Z
         beyond the factorised sweep's range guard is served too, and its Python-path products run the direct sweep)."""
-        return self._decide_lowrank(noise, lambda be, noise: type(self) is AdditiveRPOperator and
-                                    (self.shard is None or self.shard.world_size <= 1))
+        return self._decide_lowrank(noise, lambda be, noise: self.plain_unsharded)
 
     def _decide_lowrank(self, noise, mine, mass=None, sweep_guard=False):
-        """lowrank_form of this class and of its weighted subclass.  `mine(be, noise)`: the class's own conditions (its exact type
-        first), asked once the setting is on and the noise is known, before the shared ones: a symmetric float32 operator with
+        """lowrank_form of this class and of its weighted subclass.  `mine(be, noise)`: the class's own conditions, asked once
+        the setting is on and the noise is known, before the shared ones: a symmetric float32 operator with
         J <= 64 and a backend with prepare and lowrank_train_plan.  `mass()`: the diagonal mass passed as mass=, read (one host
         sync) only when a plan is asked for.  `sweep_guard`: at the default cap without panels a Z that is not fast_ok asks for
         no plan."""
-        if getattr(self, "_lowrank", None) is None:
+        if self._lowrank is None:
             self._lowrank = False
             be = _backend.get_backend()
             plan_fn, prepare = getattr(be, "lowrank_train_plan", None), getattr(be, "prepare", None)
@@ -239,13 +291,13 @@ class AdditiveRPOperator(LinearOperator):
 
     def _lowrank_in_use(self, noise=None):
         """lowrank_form(noise) under settings.lowrank_kernel or once a plan serves this operator, else None without deciding."""
-        return self.lowrank_form(noise) if (settings.lowrank_kernel.on() or getattr(self, "_lowrank", None)) else None
+        return self.lowrank_form(noise) if (settings.lowrank_kernel.on() or self._lowrank) else None
 
     def lowrank_mll_form(self, noise=None):
         """The explicit features (lowrank_mll.FeatureForm) on which settings.lowrank_mll evaluates this operator's marginal
         likelihood in closed form, or None when that mode does not serve it (the reason: `lowrank_mll_reason`).  Decided ONCE
         per operator (= per hyper-parameter step), from the noise (default: the host value the marginal likelihood recorded)."""
-        if getattr(self, "_lowrank_mll", None) is None:
+        if self._lowrank_mll is None:
             from . import lowrank_mll
             if noise is None:
                 noise = getattr(self, "_noise_host", None)
@@ -255,32 +307,28 @@ class AdditiveRPOperator(LinearOperator):
     @property
     def lowrank_mll_served(self):
         """Whether the closed-form features mode serves this operator (False while undecided)."""
-        d = getattr(self, "_lowrank_mll", None)
-        return bool(d and d[0] is not None)
+        return bool(self._lowrank_mll and self._lowrank_mll[0] is not None)
 
     @property
     def lowrank_mll_reason(self):
         """Why the features mode does not serve this operator (None when it does or while undecided)."""
-        d = getattr(self, "_lowrank_mll", None)
-        return d[1] if d else None
+        return self._lowrank_mll[1] if self._lowrank_mll else None
 
     @property
     def lowrank_served(self):
         """Whether the low-rank form serves this operator (False while undecided)."""
-        return bool(getattr(self, "_lowrank", None))
+        return bool(self._lowrank)
 
     @property
     def lowrank_ranks(self):
         """(p, q) of the low-rank form that serves this operator, or None."""
-        lr = getattr(self, "_lowrank", None)
-        return (lr.p, lr.q) if lr else None
+        return (self._lowrank.p, self._lowrank.q) if self._lowrank else None
 
     @property
     def lowrank_panels(self):
         """Panel count P >= 2 of the panel plan that serves this operator (settings.lowrank_panels), 0 for a single-interval
         plan, None when the low-rank form does not serve it."""
-        lr = getattr(self, "_lowrank", None)
-        return int(getattr(lr, "panels", 0)) if lr else None
+        return int(getattr(self._lowrank, "panels", 0)) if self._lowrank else None
 
     def native_descriptor(self, noise=0.0):
         """`struct rpgp_operator` for the native mBCG executor, or None when the operator must stay on the Python path
@@ -290,8 +338,7 @@ class AdditiveRPOperator(LinearOperator):
         be = _backend.get_backend()
         if not self.symmetric or not hasattr(be, "mbcg_solve") or self.Z1.dtype != torch.float32:
             return None
-        sharded = self.shard is not None and self.shard.world_size > 1
-        if sharded and not settings.native_sharded_cg.on():
+        if self._sharded and not settings.native_sharded_cg.on():
             return None
         from . import _lib
         z1 = self.Z1.detach()
@@ -300,7 +347,7 @@ class AdditiveRPOperator(LinearOperator):
             return be.make_operator_desc(_lib.RPGP_OP_LOWRANK, z1.shape[0], z1.shape[1], self._scale, noise, lowrank=lr)
         j0, j1 = self._jrange()
         kw = {}
-        if sharded:
+        if self._sharded:
             ps = self.shard.pair_shard(be)
             if ps is not None:
                 j0, j1 = 0, self.num_projections
@@ -317,40 +364,45 @@ class AdditiveRPOperator(LinearOperator):
 
     def native_sharding(self):
         """(mode, reducer, global_N) for the native executor, or None for an unsharded operator."""
-        if self.shard is None or self.shard.world_size <= 1:
+        if not self._sharded:
             return None
         return ("partial", self.shard.reducer, self.Z1.shape[0])
 
     def _transpose_nonbatch(self):
-        if self.symmetric:
-            return self
+        return self if self.symmetric else self._swapped()
+
+    def _swapped(self):
+        """The same operator with its two inputs exchanged (hook of `_transpose_nonbatch`; only asked of a rectangular one)."""
         return AdditiveRPOperator(self.Z2, self.Z1, self.outputscale, self.weight, self.shard)
 
     def _diagonal(self):
         if not self.symmetric:
             raise RuntimeError("diagonal of a rectangular cross-covariance requested")
-        n = self.Z1.shape[0]
-        # k(x,x) = outputscale * weight * J  (SURVEY.md A.1: diag(K) = s*w*J)
-        return torch.full((n,), self._scale * self.num_projections, dtype=self.dtype, device=self.device)
+        d = self._diagonal_value()
+        if isinstance(d, torch.Tensor):
+            return d
+        return torch.full((self.Z1.shape[0],), d, dtype=self.dtype, device=self.device)
+
+    def _diagonal_value(self):
+        """k(x, x): one value for all rows, or the backend's vector (hook of `_diagonal`)."""
+        return self._scale * self.num_projections       # (SURVEY.md A.1: diag(K) = s*w*J)
+
+    def _dense_block(self, idx=None):
+        """K[idx, :] as a dense matrix, all rows for idx = None (hook of `_get_rows` and `to_dense`)."""
+        z2 = self.Z1 if self.symmetric else self.Z2
+        return _backend.get_backend().dense(_rows(self.Z1.detach(), idx), z2.detach(), self._scale)
 
     def _get_rows(self, idx):
-        be = _backend.get_backend()
-        z2 = self.Z1 if self.symmetric else self.Z2
-        return be.dense(self.Z1.detach().index_select(0, idx).contiguous(), z2.detach(), self._scale)
+        return self._dense_block(idx)
 
     def to_dense(self):
-        be = _backend.get_backend()
-        z2 = self.Z1 if self.symmetric else self.Z2
-        return be.dense(self.Z1.detach(), z2.detach(), self._scale)
-
-    evaluate = to_dense
+        return self._dense_block()
 
     def to_dense_cached(self):
         """The matrix of the cached-K mode: same entries as to_dense(), rows padded to 256 bytes when the backend can
         (a view with stride(0) >= N), so that the HBM stream of DenseOperator runs on aligned 16-byte loads."""
         be = _backend.get_backend()
-        if type(self) is AdditiveRPOperator and self.symmetric and self.Z1.dtype == torch.float32 and \
-                getattr(be, "supports_padded_dense", False):
+        if self.plain and self.symmetric and self.Z1.dtype == torch.float32 and getattr(be, "supports_padded_dense", False):
             return be.dense(self.Z1.detach(), self.Z1.detach(), self._scale, pad=True)
         return self.to_dense()
 
@@ -359,10 +411,10 @@ class AdditiveRPOperator(LinearOperator):
         None when the backend / operator cannot provide one (then the dense matrix is the cached-K form).  `wide`: the
         matrix-core tile layout for blocks of 5..16 right-hand sides (training), else the rotation order (thin solves)."""
         be = _backend.get_backend()
-        if type(self) is not AdditiveRPOperator or not self.symmetric or self.Z1.dtype != torch.float32 or \
+        if not self.plain or not self.symmetric or self.Z1.dtype != torch.float32 or \
                 not getattr(be, "supports_symcache", False):
             return None
-        if self.shard is None or self.shard.world_size == 1:
+        if not self._sharded:
             return be.symcache(self.Z1.detach(), wide=wide)
         ps = self.shard.pair_shard(be)          # multi-GPU: this rank's share of the pairs (pair-sharding only)
         if ps is None:
@@ -370,33 +422,33 @@ class AdditiveRPOperator(LinearOperator):
         return be.symcache(self.Z1.detach(), shard=ps, wide=wide)
 
     def representation(self):
-        if self.symmetric:
-            return (self.Z1, self.outputscale)
-        return (self.Z1, self.Z2, self.outputscale)
+        zs = (self.Z1,) if self.symmetric else (self.Z1, self.Z2)
+        return zs + (self.outputscale,) + (() if self.comp_weights is None else (self.comp_weights,))
 
     def _bilinear_derivative(self, left_vecs, right_vecs):
         if not self.symmetric:
             raise NotImplementedError("derivatives are only needed for the train-train kernel")
+        return self._bilinear_grads(left_vecs.detach(), right_vecs.detach())
+
+    def _bilinear_grads(self, L, R):
+        """Hook of `_bilinear_derivative` on the symmetric operator: L, R are detached."""
         be = _backend.get_backend()
         j0, j1 = self._jrange()
         lr = self._lowrank_in_use()
         if lr is not None:
-            gZ, gs = be.bilinear_grad_lowrank(lr, left_vecs.detach(), right_vecs.detach(), self._scale)
+            gZ, gs = be.bilinear_grad_lowrank(lr, L, R, self._scale)
         elif j1 > j0:
-            gZ, gs = be.bilinear_grad(self.Z1.detach(), left_vecs.detach(), right_vecs.detach(), self._scale,
-                                      j0=j0, j1=j1)
+            gZ, gs = be.bilinear_grad(self.Z1.detach(), L, R, self._scale, j0=j0, j1=j1)
         else:
             gZ = torch.zeros_like(self.Z1)
             gs = torch.zeros((), dtype=self.dtype, device=self.device)
-        if self.shard is not None and self.shard.world_size > 1:
+        if self._sharded:
             from .distributed import all_reduce_sum_
             all_reduce_sum_(gZ, self.shard.group)
             gs = gs.reshape(1)
             all_reduce_sum_(gs, self.shard.group)
             gs = gs.reshape(())
         return gZ, (gs if self.weight == 1.0 else gs * self.weight)
-
-    _quad_form_derivative = _bilinear_derivative
 
     def dense_weight_derivative(self, S):
         """Gradients of 0.5*sum(S * self) for an explicit symmetric S (Cholesky regime)."""
@@ -410,10 +462,14 @@ class SKIAdditiveOperator(AdditiveRPOperator):
     SURVEY.md Appendix E): cubic interpolation of every projection onto one shared regular grid of `grid_size` points
     and a Toeplitz matrix of the wrapped 1-D sub-kernel (`kind`: RBF by default) on the grid.  O(N) per MVM (scatter / Toeplitz / gather kernels); same protocol as the exact
     operator so the whole solve stack is unchanged.  The grid is recomputed from the data range at construction
-    (once per hyper-parameter step) and is not differentiated (it is a buffer in GPyTorch as well)."""
+    (once per hyper-parameter step) and is not differentiated (it is a buffer in GPyTorch as well); `gp`: the grid block of the
+    operator this one is the transpose of, instead of a new one."""
+
+    plain = False
+    cacheable = False              # (its O(N) product is the point; a wide solve may still densify it: densify_for_wide_solve)
 
     def __init__(self, Z1, Z2=None, outputscale=None, weight=1.0, shard=None, grid_size=1024, comp_weights=None,
-                 row_shard=None, grid_rule="shared", kind="RBF"):
+                 row_shard=None, grid_rule="shared", kind="RBF", gp=None):
         super().__init__(Z1, Z2, outputscale, weight, shard=None)     # (no J-sharding: the SKI product is O(N))
         self.grid_size = int(grid_size)
         # the wrapped 1-D sub-kernel (training_routines.py:157-158 wraps whatever `_map_to_kernel` returned): only the
@@ -433,15 +489,18 @@ class SKIAdditiveOperator(AdditiveRPOperator):
         # `GridInterpolationKernel(kernel, **ski_options)` at training_routines.py:157-158 passes no bounds); "reference" =
         # the per-projection bounds of polynomial_projection_kernels.py:54-63 (rp_poly / strictly_additive / additive kinds)
         self.grid_rule = grid_rule
-        be = _backend.get_backend()
-        kw = {} if grid_rule == "shared" else {"rule": grid_rule}
-        if kind != "RBF":
-            kw["kind"] = kind
-        if comp_weights is None:
-            self.gp = be.ski_grid(Z1.detach(), None if Z2 is None else Z2.detach(), self.grid_size, **kw)
-        else:
-            self.gp = be.ski_grid(Z1.detach(), None if Z2 is None else Z2.detach(), self.grid_size,
-                                  weights=comp_weights.detach(), **kw)
+        if gp is None:
+            kw = {} if grid_rule == "shared" else {"rule": grid_rule}
+            if kind != "RBF":
+                kw["kind"] = kind
+            if comp_weights is not None:
+                kw = dict(weights=comp_weights.detach(), **kw)
+            gp = _backend.get_backend().ski_grid(Z1.detach(), None if Z2 is None else Z2.detach(), self.grid_size, **kw)
+        self.gp = gp
+
+    def densify_for_wide_solve(self, n):
+        # the operator's own wide scatter / gather is O(N J T) and wins above N ~ 32k (models.PredictionStrategy.solve)
+        return n <= 32768
 
     def fused_pivoted_cholesky(self, rank):
         be = _backend.get_backend()
@@ -479,24 +538,10 @@ class SKIAdditiveOperator(AdditiveRPOperator):
         return be.make_operator_desc(_lib.RPGP_OP_SKI, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1, gp=self.gp,
                                      G=self.grid_size, prep=self._get_plan())
 
-    def native_sharding(self):
-        return None
-
-    def _matmul(self, rhs, noise=0.0):
-        if noise and not self.symmetric:
-            raise ValueError("a diagonal can only be added to the square symmetric operator")
-        return self._local_matmul(rhs.detach(), noise)
-
-    def _transpose_nonbatch(self):
-        if self.symmetric:
-            return self
-        t = SKIAdditiveOperator.__new__(SKIAdditiveOperator)
-        AdditiveRPOperator.__init__(t, self.Z2, self.Z1, self.outputscale, self.weight, None)
-        t.grid_size, t.gp, t.comp_weights, t.row_shard, t._plan = self.grid_size, self.gp, self.comp_weights, None, None
-        t._local_plan = None
-        t.grid_rule = self.grid_rule
-        t.kind = self.kind
-        return t
+    def _swapped(self):
+        # on the SAME grid block (building one is a backend call and a host sync); no row shard, and the plans start empty
+        return SKIAdditiveOperator(self.Z2, self.Z1, self.outputscale, self.weight, grid_size=self.grid_size,
+                                   comp_weights=self.comp_weights, grid_rule=self.grid_rule, kind=self.kind, gp=self.gp)
 
     def row_sharded(self, noise):
         """This rank's rows of (self + noise I) as a RowShardedSKIOperator on the SAME grid block (and weights)."""
@@ -549,73 +594,48 @@ class SKIAdditiveOperator(AdditiveRPOperator):
             return gZ, tail[0] * self.weight, self._scale * tail[1:] / w
         return gZ, tail[0] * self.weight
 
-    def _diagonal(self):
-        if not self.symmetric:
-            raise RuntimeError("diagonal of a rectangular cross-covariance requested")
+    def _diagonal_value(self):
         return _backend.get_backend().ski_diag(self.Z1.detach(), self.gp, self._scale, self.grid_size)
 
-    def representation(self):
-        base = super().representation()
-        return base if self.comp_weights is None else base + (self.comp_weights,)
-
-    def _get_rows(self, idx):
-        be = _backend.get_backend()
-        z1 = self.Z1.detach()
-        z2 = z1 if self.symmetric else self.Z2.detach()
-        if hasattr(be, "ski_dense") and z1.shape[1] <= 64:
-            return be.ski_dense(z1.index_select(0, idx).contiguous(), z2, self.gp, self._scale, self.grid_size)
-        k = idx.numel()
-        eye = torch.eye(k, dtype=self.dtype, device=self.device)
-        # K[idx, :] = (K(Z2, Z1[idx]))^T : interpolate the k selected points, gather at all columns
-        cols = be.ski_mvm(z2, z1.index_select(0, idx).contiguous(), self.gp, eye, self._scale, 0.0, self.grid_size)
-        return cols.t().contiguous()
-
-    def to_dense(self):
+    def _dense_block(self, idx=None):
         be = _backend.get_backend()
         z1 = self.Z1.detach()
         z2 = z1 if self.symmetric else self.Z2.detach()
         if hasattr(be, "ski_dense") and z1.shape[1] <= 64:
             # straight from the interpolation weights and the Toeplitz lags (no N x N identity through the MVM)
-            return be.ski_dense(z1, z2, self.gp, self._scale, self.grid_size)
-        eye = torch.eye(z2.shape[0], dtype=self.dtype, device=self.device)
-        return be.ski_mvm(z1, z2, self.gp, eye, self._scale, 0.0, self.grid_size)
+            return be.ski_dense(_rows(z1, idx), z2, self.gp, self._scale, self.grid_size)
+        if idx is None:
+            eye = torch.eye(z2.shape[0], dtype=self.dtype, device=self.device)
+            return be.ski_mvm(z1, z2, self.gp, eye, self._scale, 0.0, self.grid_size)
+        eye = torch.eye(idx.numel(), dtype=self.dtype, device=self.device)
+        # K[idx, :] = (K(Z2, Z1[idx]))^T : interpolate the k selected points, gather at all columns
+        return be.ski_mvm(z2, _rows(z1, idx), self.gp, eye, self._scale, 0.0, self.grid_size).t().contiguous()
 
-    evaluate = to_dense
-
-    def _bilinear_derivative(self, left_vecs, right_vecs):
-        if not self.symmetric:
-            raise NotImplementedError("derivatives are only needed for the train-train kernel")
+    def _bilinear_grads(self, L, R):
         be = _backend.get_backend()
+        z, comp = self.Z1.detach(), self.comp_weights is not None
         plan = self._get_plan()
         if plan is not None and hasattr(be, "ski_bilinear_scatter"):
             # staged form on the operator's plan: cell-sorted scatters of L and R (no atomics), the 2T-column Toeplitz product
             # on the matrix cores, then the per-row derivative — 12 columns per piece
-            z = self.Z1.detach()
-            comp = self.comp_weights is not None
             gZ = gs = gc = None
-            for t0 in range(0, left_vecs.shape[1], 12):
-                Lc = left_vecs[:, t0:t0 + 12].detach().contiguous()
-                Rc = right_vecs[:, t0:t0 + 12].detach().contiguous()
+            for t0 in range(0, L.shape[1], 12):
+                Lc = L[:, t0:t0 + 12].contiguous()
+                Rc = R[:, t0:t0 + 12].contiguous()
                 hist = be.ski_bilinear_scatter(z, self.gp, Lc, Rc, self.grid_size, plan=plan)
                 gz_p, gs_p, gc_p = be.ski_bilinear_finish(z, self.gp, hist, Lc, Rc, self._scale, self.grid_size, comp=comp)
                 gZ = gz_p if gZ is None else gZ.add_(gz_p)
                 gs = gs_p if gs is None else gs.add_(gs_p)
                 if comp:
                     gc = gc_p if gc is None else gc.add_(gc_p)
-            if comp:
-                w = self.comp_weights.detach().to(gc)
-                return gZ, gs * self.weight, self._scale * gc / w
-            return gZ, gs * self.weight
-        if self.comp_weights is not None:
-            gZ, gs, gc = be.ski_bilinear_grad_comp(self.Z1.detach(), self.gp, left_vecs.detach(), right_vecs.detach(),
-                                                   self._scale, self.grid_size)
+        elif comp:
+            gZ, gs, gc = be.ski_bilinear_grad_comp(z, self.gp, L, R, self._scale, self.grid_size)
+        else:
+            gZ, gs = be.ski_bilinear_grad(z, self.gp, L, R, self._scale, self.grid_size)
+        if comp:
             w = self.comp_weights.detach().to(gc)
             return gZ, gs * self.weight, self._scale * gc / w       # d/dZ, d/d outputscale, d/d comp_weights
-        gZ, gs = be.ski_bilinear_grad(self.Z1.detach(), self.gp, left_vecs.detach(), right_vecs.detach(), self._scale,
-                                      self.grid_size)
         return gZ, gs * self.weight
-
-    _quad_form_derivative = _bilinear_derivative
 
     def dense_weight_derivative(self, S):
         """Gradients of 0.5*sum(S * self) for an explicit symmetric S: bilinear form with L = S/2, R = I."""
@@ -845,7 +865,20 @@ def row_sharded_preconditioner(op, rank):
     return RowShardedWoodbury(L.t().contiguous(), op._noise, sh)
 
 
-class FamilyAdditiveOperator(AdditiveRPOperator):
+class _WeightedOperator(AdditiveRPOperator):
+    """What the family, full and mixed-group operators share: a sum of components phi(.) with phi(0) = 1 and output scales
+    summing to `_wsum`, replicated (no shard, no operator weight), and none of the plain operator's own fast paths."""
+
+    plain = False
+
+    def __init__(self, Z1, Z2, outputscale):
+        super().__init__(Z1, Z2, outputscale, 1.0, shard=None)
+
+    def _diagonal_value(self):
+        return self._scale * self._wsum             # k(x, x) = outputscale * sum_c w_c
+
+
+class FamilyAdditiveOperator(_WeightedOperator):
     """K = outputscale * sum_c w_c phi_kind(group c of Z's columns) — the other members of the family behind the same
     operator: `kernel_type` Matern / InverseMQ / Cosine sub-kernels (training_routines.py:47-88),
     k > 1 RBF sub-kernels (:172-174) and per-component output scales (polynomial_projection_kernels.py:88-98).
@@ -853,7 +886,7 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
     (rpgp_family_*); runs replicated (no J-sharding), fp32 only."""
 
     def __init__(self, Z1, Z2=None, outputscale=None, comp_weights=None, kind="RBF", group=1, product=False):
-        super().__init__(Z1, Z2, outputscale, 1.0, shard=None)
+        super().__init__(Z1, Z2, outputscale)
         self.kind, self.group = kind, int(group)
         # a k > 1 group as the PRODUCT of its 1-D sub-kernels (polynomial_projection_kernels.py:70-86) instead of the radial
         # k-dimensional sub-kernel of `additive_rp` (training_routines.py:172-174); one and the same for the RBF
@@ -873,6 +906,15 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         self._generic = bool(getattr(self.fam, "generic", False))
         self._wsum = float(w.sum())                 # one host sync per construction (= per optimiser step)
 
+    @property
+    def _one_form(self):
+        """ONE Chebyshev form serves every column: 1-D RBF components (a weight is a factor, a lengthscale is in the column)."""
+        return self.kind == "RBF" and self.group == 1 and not self.product
+
+    @property
+    def feature_form_kind(self):
+        return "weighted" if self._one_form and self.symmetric else None
+
     def lowrank_form(self, noise=None):
         """The plain operator's protocol for the weighted kinds: the training plan of the ONE Chebyshev form shared by every
         column of Z (the lengthscales are folded into the columns; a component weight is a factor of the combine pass) that
@@ -881,8 +923,7 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         a plan with p, q <= settings.lowrank_max_rank (64 by default) at the tolerance of the kernel's diagonal mass scale * sum_c |w_c| (weights of any sign: the
         product is linear in them).  Decided ONCE per operator, like the plain operator's."""
         def mine(be, noise):
-            return type(self) is FamilyAdditiveOperator and self.kind == "RBF" and self.group == 1 and not self.product and \
-                not self._generic and hasattr(be, "mvm_sym_lowrank_weighted") and \
+            return self._one_form and not self._generic and hasattr(be, "mvm_sym_lowrank_weighted") and \
                 hasattr(be, "bilinear_grad_lowrank_weighted") and float(noise) > 0.0
 
         # (sweep_guard: above 64 or with panels the plan decides on a finite range; at the defaults the sweep's guard does)
@@ -893,16 +934,10 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         be = _backend.get_backend()
         z1 = self.Z1.detach()
         if self.symmetric:
-            lr = getattr(self, "_lowrank", None)       # (only a plan decided under settings.lowrank_kernel: lowrank_form)
-            if lr:
-                return be.mvm_sym_lowrank_weighted(lr, self._prep, self.fam.weights, rhs, self._scale, noise)
+            if self._lowrank:                           # (only a plan decided under settings.lowrank_kernel: lowrank_form)
+                return be.mvm_sym_lowrank_weighted(self._lowrank, self._prep, self.fam.weights, rhs, self._scale, noise)
             return be.family_mvm_sym(self.fam, z1, rhs, self._scale, noise)
         return be.family_mvm_rect(self.fam, z1, self.Z2.detach(), rhs, self._scale)
-
-    def _matmul(self, rhs, noise=0.0):
-        if noise and not self.symmetric:
-            raise ValueError("a diagonal can only be added to the square symmetric operator")
-        return self._local_matmul(rhs.detach(), noise if self.symmetric else 0.0)
 
     def fused_pivoted_cholesky(self, rank):
         be = _backend.get_backend()
@@ -925,101 +960,141 @@ class FamilyAdditiveOperator(AdditiveRPOperator):
         return be.make_operator_desc(_lib.RPGP_OP_FAMILY, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1,
                                      family=self.fam)
 
-    def native_sharding(self):
-        return None
-
-    def _transpose_nonbatch(self):
-        if self.symmetric:
-            return self
+    def _swapped(self):
         return FamilyAdditiveOperator(self.Z2, self.Z1, self.outputscale, self.comp_weights, self.kind, self.group, self.product)
 
-    def _diagonal(self):
-        if not self.symmetric:
-            raise RuntimeError("diagonal of a rectangular cross-covariance requested")
-        # phi(0) = 1 for every member: k(x,x) = outputscale * sum_c w_c
-        return torch.full((self.Z1.shape[0],), self._scale * self._wsum, dtype=self.dtype, device=self.device)
-
-    def _get_rows(self, idx):
-        be = _backend.get_backend()
+    def _dense_block(self, idx=None):
         z2 = self.Z1 if self.symmetric else self.Z2
-        return be.family_dense(self.fam, self.Z1.detach().index_select(0, idx).contiguous(), z2.detach(), self._scale)
-
-    def to_dense(self):
-        be = _backend.get_backend()
-        z2 = self.Z1 if self.symmetric else self.Z2
-        return be.family_dense(self.fam, self.Z1.detach(), z2.detach(), self._scale)
-
-    evaluate = to_dense
-
-    def representation(self):
-        if self.symmetric:
-            return (self.Z1, self.outputscale, self.comp_weights)
-        return (self.Z1, self.Z2, self.outputscale, self.comp_weights)
+        return _backend.get_backend().family_dense(self.fam, _rows(self.Z1.detach(), idx), z2.detach(), self._scale)
 
     def _finish_grads(self, gZ, gcomp):
         w = self.comp_weights.detach().to(gcomp)
         return gZ, (w * gcomp).sum(), self._scale * gcomp          # d/dZ, d/d outputscale, d/d comp_weights
 
-    def _bilinear_derivative(self, left_vecs, right_vecs):
-        if not self.symmetric:
-            raise NotImplementedError("derivatives are only needed for the train-train kernel")
+    def _bilinear_grads(self, L, R):
         be = _backend.get_backend()
         lr = self._lowrank_in_use()
         if lr is not None:
-            gZ, gc = be.bilinear_grad_lowrank_weighted(lr, self.fam.weights, left_vecs.detach(), right_vecs.detach(),
-                                                       self._scale)
-        else:
-            gZ, gc = be.family_bilinear_grad(self.fam, self.Z1.detach(), left_vecs.detach(), right_vecs.detach(), self._scale)
-        return self._finish_grads(gZ, gc)
-
-    _quad_form_derivative = _bilinear_derivative
+            return self._finish_grads(*be.bilinear_grad_lowrank_weighted(lr, self.fam.weights, L, R, self._scale))
+        return self._finish_grads(*be.family_bilinear_grad(self.fam, self.Z1.detach(), L, R, self._scale))
 
     def dense_weight_derivative(self, S):
-        gZ, gc = _backend.get_backend().family_bilinear_grad_dense(self.fam, self.Z1.detach(), S, self._scale)
-        return self._finish_grads(gZ, gc)
+        return self._finish_grads(*_backend.get_backend().family_bilinear_grad_dense(self.fam, self.Z1.detach(), S, self._scale))
 
 
-class FullKernelOperator(AdditiveRPOperator):
+class _FamilyRoute:
+    """A full RBF kernel with d <= 20 columns as ONE component of group g >= d of the family tile kernels: owns the zero columns
+    up to the instantiated group size g, and takes them off the derivatives again."""
+
+    def __init__(self, fam, Z1, Z2, g):
+        self.fam, self.d = fam, Z1.shape[1]
+
+        def pad(Z):
+            return None if Z is None else torch.nn.functional.pad(Z.detach(), (0, g - self.d)).contiguous()
+        self.z1, self.z2 = pad(Z1), pad(Z2)
+
+    def matmul(self, be, rhs, scale, noise):
+        if self.z2 is None:
+            return be.family_mvm_sym(self.fam, self.z1, rhs, scale, noise)
+        return be.family_mvm_rect(self.fam, self.z1, self.z2, rhs, scale)
+
+    def dense(self, be, idx, scale):
+        return be.family_dense(self.fam, _rows(self.z1, idx), self.z1 if self.z2 is None else self.z2, scale)
+
+    def _unpadded(self, gZ, gc):
+        return gZ[:, :self.d].contiguous(), gc.reshape(-1)[0]
+
+    def bilinear_grad(self, be, L, R, scale):
+        return self._unpadded(*be.family_bilinear_grad(self.fam, self.z1, L, R, scale))
+
+    def bilinear_grad_dense(self, be, S, scale):
+        return self._unpadded(*be.family_bilinear_grad_dense(self.fam, self.z1, S, scale))
+
+    def descriptor(self, be, scale, noise):
+        from . import _lib
+        z1 = self.z1
+        return be.make_operator_desc(_lib.RPGP_OP_FAMILY, z1.shape[0], z1.shape[1], scale, noise, Z=z1, family=self.fam)
+
+
+class _RadialRoute:
+    """A full kernel of any kind and d <= 1024 on the radial kernels (csrc/rpgp_radial.hip): owns the radial family of the native
+    executor, made on first use."""
+
+    def __init__(self, kind, Z1, Z2):
+        self.kind, self.z1, self.z2, self.fam = kind, Z1.detach(), None if Z2 is None else Z2.detach(), None
+
+    def matmul(self, be, rhs, scale, noise):
+        return be.radial_mvm(self.kind, self.z1, self.z2, rhs, scale, noise if self.z2 is None else 0.0)
+
+    def dense(self, be, idx, scale):
+        z1 = self.z1.contiguous()
+        rows = be.radial_dense(self.kind, _rows(z1, idx), z1 if self.z2 is None else self.z2, scale)
+        if idx is not None and self.z2 is None:
+            # the selected rows are a copy, so the kernel cannot know which entries are diagonal ones: they get the value
+            # _diagonal() claims, scale * phi(0), exactly as in the product and the square dense block
+            rows[torch.arange(idx.numel(), device=rows.device), idx] = scale
+        return rows
+
+    def bilinear_grad(self, be, L, R, scale):
+        return be.radial_bilinear_grad(self.kind, self.z1, L, R, scale)
+
+    def bilinear_grad_dense(self, be, S, scale):
+        return be.radial_bilinear_grad_dense(self.kind, self.z1, S, scale)
+
+    def descriptor(self, be, scale, noise):
+        if not hasattr(be, "make_radial_family"):
+            return None
+        from . import _lib
+        if self.fam is None:
+            self.fam = be.make_radial_family(self.kind, self.z1.shape[1])
+        z1 = self.z1.contiguous()
+        return be.make_operator_desc(_lib.RPGP_OP_RADIAL, z1.shape[0], z1.shape[1], scale, noise, Z=z1, family=self.fam)
+
+
+class FullKernelOperator(_WeightedOperator):
     """K = outputscale * phi_kind(|z_i - z_i'|^2) over ALL d columns of Z — the `full` kinds (training_routines.py:275-293: one
     RBF / Matern / InverseMQ / Cosine kernel on all inputs, ARD or not) matrix-free (settings.fused_full): the family's single
     component of group = d on the radial kernels (csrc/rpgp_radial.hip), whose squared distance is a Gram product on the fp32
     matrix cores, for any d <= 1024.  Z is already CENTRED (the Gram form's rounding error grows with the norms of the rows,
     not with their distance) and divided by the lengthscales, both inside autograd, so that the lengthscale gradient comes
     from gZ by the chain rule.  Same protocol as the additive operators: the marginal likelihood and the prediction strategy
-    take their CG / SLQ / pivoted-Cholesky / LOVE routes.  Unsharded, float32, never cached as an N x N matrix."""
+    take their CG / SLQ / pivoted-Cholesky / LOVE routes.  Unsharded, float32, never cached as an N x N matrix.  Which kernels
+    evaluate it (`_route`: _FamilyRoute or _RadialRoute) is chosen once per operator."""
 
     cacheable = False              # (solve_operator / PredictionStrategy: no dense or packed copy of K; the product is the point)
+    _wsum = 1.0                    # one component: phi(0) = 1, and the symmetric product forces d2 = 0 on the diagonal, so
+    #                                k(x, x) = outputscale exactly
 
     def __init__(self, Z1, Z2=None, outputscale=None, kind="RBF"):
-        super().__init__(Z1, Z2, outputscale, 1.0, shard=None)
+        super().__init__(Z1, Z2, outputscale)
         self.kind = kind
-        self._fam = None
-        self._route = None          # None undecided, False the radial kernels, else (family, padded Z1, padded Z2 or None)
+        self._chosen = None
 
-    def _family_route(self):
-        """The RBF with d <= 20 columns as ONE component of group d of the family tile kernels (zero columns up to the next
-        instantiated group size): (family, padded Z1, padded Z2 or None) for the backend's family_* entries, or None for the
-        radial kernels.  Measured on the MI355X at N = 50 000: the tile kernel takes 0.8 / 1.4 ms (T = 1) and
-        2.1 / 2.7 ms (T = 11) at d = 8 / 20 against 4.0 - 4.7 ms of the radial kernel, far beyond the 5 % spread; the other kinds
-        have no tile kernel for a radial group, and d > 20 none at all.  The entries are called directly (no
-        FamilyAdditiveOperator in between: no low-rank decision of its own, no host read of the weight); `_FULL_FAMILY_ROUTE`
-        (private: tools/radial_bench.py times both) switches the route off."""
-        if self._route is None:
+    @property
+    def _route(self):
+        """The RBF with d <= 20 columns on the family tile kernels, everything else on the radial kernels.  Measured on the MI355X
+        at N = 50 000: the tile kernel takes 0.8 / 1.4 ms (T = 1) and 2.1 / 2.7 ms (T = 11) at d = 8 / 20 against
+        4.0 - 4.7 ms of the radial kernel, far beyond the 5 % spread; the other kinds have no tile kernel for a radial group, and
+        d > 20 none at all.  The entries are called directly (no FamilyAdditiveOperator in between: no low-rank decision of its
+        own, no host read of the weight); `_FULL_FAMILY_ROUTE` (private: tools/radial_bench.py times both) switches the family
+        route off."""
+        if self._chosen is None:
             be = _backend.get_backend()
             d = self.Z1.shape[1]
             names = ("make_family", "family_mvm_sym", "family_mvm_rect", "family_dense", "family_bilinear_grad",
                      "family_bilinear_grad_dense")
-            if not _FULL_FAMILY_ROUTE or self.kind != "RBF" or d > _FAMILY_GROUPS[-1] or self.Z1.dtype != torch.float32 or \
-                    not all(hasattr(be, n) for n in names):
-                self._route = False
-            else:
+            self._chosen = _RadialRoute(self.kind, self.Z1, self.Z2)
+            if _FULL_FAMILY_ROUTE and self.kind == "RBF" and d <= _FAMILY_GROUPS[-1] and self.Z1.dtype == torch.float32 and \
+                    all(hasattr(be, n) for n in names):
                 g = padded_group_size(d)
-
-                def pad(Z):
-                    return None if Z is None else torch.nn.functional.pad(Z.detach(), (0, g - d)).contiguous()
                 fam = be.make_family("RBF", g, torch.ones(1, dtype=torch.float32, device=self.Z1.device))
-                self._route = False if getattr(fam, "generic", False) else (fam, pad(self.Z1), pad(self.Z2))
-        return self._route or None
+                if not getattr(fam, "generic", False):
+                    self._chosen = _FamilyRoute(fam, self.Z1, self.Z2, g)
+        return self._chosen
+
+    def _family_route(self):
+        """The family route when it serves this operator, None on the radial kernels."""
+        return self._route if isinstance(self._route, _FamilyRoute) else None
 
     def lowrank_form(self, noise=None):
         return None
@@ -1028,123 +1103,29 @@ class FullKernelOperator(AdditiveRPOperator):
         self._lowrank_mll = (None, "the full kernel has no low-rank feature form")
         return None
 
-    def fused_pivoted_cholesky(self, rank):
-        return None                # (the torch loop over _get_rows builds the preconditioner)
-
-    def to_symcache(self, wide=False):
-        return None
-
     def _local_matmul(self, rhs, noise=0.0):
-        route = self._family_route()
-        be = _backend.get_backend()
-        if route is not None:
-            fam, z1, z2 = route
-            if self.symmetric:
-                return be.family_mvm_sym(fam, z1, rhs, self._scale, noise)
-            return be.family_mvm_rect(fam, z1, z2, rhs, self._scale)
-        return be.radial_mvm(self.kind, self.Z1.detach(), None if self.symmetric else self.Z2.detach(), rhs, self._scale,
-                             noise if self.symmetric else 0.0)
-
-    def _matmul(self, rhs, noise=0.0):
-        if noise and not self.symmetric:
-            raise ValueError("a diagonal can only be added to the square symmetric operator")
-        return self._local_matmul(rhs.detach(), noise)
+        return self._route.matmul(_backend.get_backend(), rhs, self._scale, noise)
 
     def native_descriptor(self, noise=0.0):
-        be = _backend.get_backend()
-        route = self._family_route()
+        be, route = _backend.get_backend(), self._route
         if not self.symmetric or not hasattr(be, "mbcg_solve"):
             return None
-        from . import _lib
-        if route is not None:
-            fam, z1, _ = route
-            return be.make_operator_desc(_lib.RPGP_OP_FAMILY, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1, family=fam)
-        if not hasattr(be, "make_radial_family"):
-            return None
-        if self._fam is None:
-            self._fam = be.make_radial_family(self.kind, self.Z1.shape[1])
-        z1 = self.Z1.detach().contiguous()
-        return be.make_operator_desc(_lib.RPGP_OP_RADIAL, z1.shape[0], z1.shape[1], self._scale, noise, Z=z1, family=self._fam)
+        return route.descriptor(be, self._scale, noise)
 
-    def native_sharding(self):
-        return None
-
-    def _transpose_nonbatch(self):
-        if self.symmetric:
-            return self
+    def _swapped(self):
         return FullKernelOperator(self.Z2, self.Z1, self.outputscale, self.kind)
 
-    def _diagonal(self):
-        if not self.symmetric:
-            raise RuntimeError("diagonal of a rectangular cross-covariance requested")
-        # phi(0) = 1 for every member, and the symmetric product forces d2 = 0 on the diagonal: k(x, x) = outputscale exactly
-        return torch.full((self.Z1.shape[0],), self._scale, dtype=self.dtype, device=self.device)
+    def _dense_block(self, idx=None):
+        return self._route.dense(_backend.get_backend(), idx, self._scale)
 
-    def _get_rows(self, idx):
-        route = self._family_route()
-        be = _backend.get_backend()
-        if route is not None:
-            fam, z1, z2 = route
-            return be.family_dense(fam, z1.index_select(0, idx).contiguous(), z1 if self.symmetric else z2, self._scale)
-        z2 = self.Z1 if self.symmetric else self.Z2
-        rows = be.radial_dense(self.kind, self.Z1.detach().index_select(0, idx).contiguous(), z2.detach(), self._scale)
-        if self.symmetric:
-            # the selected rows are a copy, so the kernel cannot know which entries are diagonal ones: they get the value
-            # _diagonal() claims, scale * phi(0), exactly as in the product and the square dense block
-            rows[torch.arange(idx.numel(), device=rows.device), idx] = self._scale
-        return rows
-
-    def to_dense(self):
-        route = self._family_route()
-        be = _backend.get_backend()
-        if route is not None:
-            fam, z1, z2 = route
-            return be.family_dense(fam, z1, z1 if self.symmetric else z2, self._scale)
-        z1 = self.Z1.detach().contiguous()
-        return be.radial_dense(self.kind, z1, z1 if self.symmetric else self.Z2.detach(), self._scale)
-
-    evaluate = to_dense
-
-    def to_dense_cached(self):
-        return self.to_dense()
-
-    def _bilinear_derivative(self, left_vecs, right_vecs):
-        if not self.symmetric:
-            raise NotImplementedError("derivatives are only needed for the train-train kernel")
-        route = self._family_route()
-        if route is not None:
-            gZ, gc = _backend.get_backend().family_bilinear_grad(route[0], route[1], left_vecs.detach(), right_vecs.detach(),
-                                                                 self._scale)
-            return gZ[:, :self.Z1.shape[1]].contiguous(), gc.reshape(-1)[0]
-        return _backend.get_backend().radial_bilinear_grad(self.kind, self.Z1.detach(), left_vecs.detach(),
-                                                           right_vecs.detach(), self._scale)
-
-    _quad_form_derivative = _bilinear_derivative
+    def _bilinear_grads(self, L, R):
+        return self._route.bilinear_grad(_backend.get_backend(), L, R, self._scale)
 
     def dense_weight_derivative(self, S):
-        route = self._family_route()
-        if route is not None:
-            gZ, gc = _backend.get_backend().family_bilinear_grad_dense(route[0], route[1], S, self._scale)
-            return gZ[:, :self.Z1.shape[1]].contiguous(), gc.reshape(-1)[0]
-        return _backend.get_backend().radial_bilinear_grad_dense(self.kind, self.Z1.detach(), S, self._scale)
+        return self._route.bilinear_grad_dense(_backend.get_backend(), S, self._scale)
 
 
-# group sizes the family tile kernels are instantiated for (ops.FAMILY_GROUPS); other sizes are padded with zero columns
-_FAMILY_GROUPS = (1, 2, 3, 4, 5, 8, 10, 20)
-# FullKernelOperator._family_route (private: False keeps every full kernel on the radial kernels, for measurements)
-_FULL_FAMILY_ROUTE = True
-
-
-def padded_group_size(k):
-    """Smallest instantiated group size >= k (an RBF group padded with all-zero coordinates is the same kernel:
-    exp(-0.5 sum d^2) gains factors exp(0))."""
-    for g in _FAMILY_GROUPS:
-        if g >= k:
-            return g
-    raise NotImplementedError("multiplicative groups of more than %d dimensions are not built" % _FAMILY_GROUPS[-1])
-
-
-class MixedGroupOperator(AdditiveRPOperator):
+class MixedGroupOperator(_WeightedOperator):
     """K = outputscale * sum_c w_c prod_{m in group c} k1(z_m - z_m') with multiplicative groups of DIFFERENT sizes
     (`general_rp_poly` with e.g. degrees [1, 1, 2, 3], training_routines.py:192-207; `create_multi_additive_kernel`,
     :247-258: every feature subset up to a degree).  The components are bucketed by group size and every bucket is one
@@ -1153,7 +1134,7 @@ class MixedGroupOperator(AdditiveRPOperator):
     executor as an RPGP_OP_SUM of the buckets."""
 
     def __init__(self, Z1, Z2=None, outputscale=None, comp_weights=None, kind="RBF", degrees=(1,), product=False):
-        super().__init__(Z1, Z2, outputscale, 1.0, shard=None)
+        super().__init__(Z1, Z2, outputscale)
         self.kind = kind
         self.product = bool(product)
         self.degrees = [int(dg) for dg in degrees]
@@ -1166,7 +1147,7 @@ class MixedGroupOperator(AdditiveRPOperator):
         starts = [0]
         for dg in self.degrees:
             starts.append(starts[-1] + dg)
-        self.buckets = []                           # (component indices, column indices, operator) per distinct size
+        self.buckets = []               # (component indices, column indices, operator, group size before padding) per distinct size
         def gather(Zm, co, k, kp, ncomp):
             z = Zm.detach().index_select(1, co)
             if kp == k:
@@ -1184,24 +1165,19 @@ class MixedGroupOperator(AdditiveRPOperator):
             z1 = gather(Z1, co, k, kp, len(comps))
             z2 = None if Z2 is None else gather(Z2, co, k, kp, len(comps))
             part = FamilyAdditiveOperator(z1, z2, outputscale, comp_weights.detach().index_select(0, ci), kind, kp, product)
-            part._true_group = k
-            self.buckets.append((ci, co, part))
-        self._wsum = sum(part._wsum for _, _, part in self.buckets)
+            self.buckets.append((ci, co, part, k))
+        self._wsum = sum(bucket[2]._wsum for bucket in self.buckets)
 
-    def _local_matmul(self, rhs, noise=0.0):
+    def _bucket_sum(self, term):
+        """Sum of term(bucket's operator, whether it is the first one: the noise rides on the first only) over the buckets."""
         out = None
-        for i, (_, _, part) in enumerate(self.buckets):
-            o = part._local_matmul(rhs, noise if i == 0 else 0.0)
+        for i, bucket in enumerate(self.buckets):
+            o = term(bucket[2], i == 0)
             out = o if out is None else out.add_(o)
         return out
 
-    def _matmul(self, rhs, noise=0.0):
-        if noise and not self.symmetric:
-            raise ValueError("a diagonal can only be added to the square symmetric operator")
-        return self._local_matmul(rhs.detach(), noise if self.symmetric else 0.0)
-
-    def fused_pivoted_cholesky(self, rank):
-        return None
+    def _local_matmul(self, rhs, noise=0.0):
+        return self._bucket_sum(lambda part, first: part._local_matmul(rhs, noise if first else 0.0))
 
     def native_descriptor(self, noise=0.0):
         """RPGP_OP_SUM of the buckets' RPGP_OP_FAMILY descriptors (the noise rides on the first one)."""
@@ -1209,59 +1185,25 @@ class MixedGroupOperator(AdditiveRPOperator):
         if not self.symmetric or not hasattr(be, "make_sum_operator_desc"):
             return None
         parts = []
-        for i, (_, _, part) in enumerate(self.buckets):
-            made = part.native_descriptor(noise if i == 0 else 0.0)
+        for i, bucket in enumerate(self.buckets):
+            made = bucket[2].native_descriptor(noise if i == 0 else 0.0)
             if made is None:
                 return None
             parts.append(made)
         return be.make_sum_operator_desc(parts)
 
-    def native_sharding(self):
-        return None
-
-    def _transpose_nonbatch(self):
-        if self.symmetric:
-            return self
+    def _swapped(self):
         return MixedGroupOperator(self.Z2, self.Z1, self.outputscale, self.comp_weights, self.kind, self.degrees, self.product)
 
-    def _diagonal(self):
-        if not self.symmetric:
-            raise RuntimeError("diagonal of a rectangular cross-covariance requested")
-        return torch.full((self.Z1.shape[0],), self._scale * self._wsum, dtype=self.dtype, device=self.device)
-
-    def _get_rows(self, idx):
-        out = None
-        for _, _, part in self.buckets:
-            o = part._get_rows(idx)
-            out = o if out is None else out.add_(o)
-        return out
-
-    def to_dense(self):
-        out = None
-        for _, _, part in self.buckets:
-            o = part.to_dense()
-            out = o if out is None else out.add_(o)
-        return out
-
-    evaluate = to_dense
-
-    def to_dense_cached(self):
-        return self.to_dense()
-
-    def to_symcache(self, wide=False):
-        return None
-
-    def representation(self):
-        if self.symmetric:
-            return (self.Z1, self.outputscale, self.comp_weights)
-        return (self.Z1, self.Z2, self.outputscale, self.comp_weights)
+    def _dense_block(self, idx=None):
+        return self._bucket_sum(lambda part, first: part._dense_block(idx))
 
     def _assemble(self, grads):
         gZ = torch.zeros_like(self.Z1)
         gc = torch.zeros(len(self.degrees), dtype=self.Z1.dtype, device=self.Z1.device)
         gs = torch.zeros((), dtype=self.Z1.dtype, device=self.Z1.device)
-        for (ci, co, part), (gz_p, gs_p, gc_p) in zip(self.buckets, grads):
-            k, kp = part._true_group, part.group
+        for (ci, co, part, k), (gz_p, gs_p, gc_p) in zip(self.buckets, grads):
+            kp = part.group
             if kp != k:                              # drop the derivatives of the padding columns
                 gz_p = gz_p.reshape(gz_p.shape[0], -1, kp)[:, :, :k].reshape(gz_p.shape[0], -1)
             gZ.index_copy_(1, co, gz_p.to(gZ))
@@ -1269,15 +1211,11 @@ class MixedGroupOperator(AdditiveRPOperator):
             gs = gs + gs_p.to(gs)
         return gZ, gs, gc
 
-    def _bilinear_derivative(self, left_vecs, right_vecs):
-        if not self.symmetric:
-            raise NotImplementedError("derivatives are only needed for the train-train kernel")
-        return self._assemble([part._bilinear_derivative(left_vecs, right_vecs) for _, _, part in self.buckets])
-
-    _quad_form_derivative = _bilinear_derivative
+    def _bilinear_grads(self, L, R):
+        return self._assemble([bucket[2]._bilinear_grads(L, R) for bucket in self.buckets])
 
     def dense_weight_derivative(self, S):
-        return self._assemble([part.dense_weight_derivative(S) for _, _, part in self.buckets])
+        return self._assemble([bucket[2].dense_weight_derivative(S) for bucket in self.buckets])
 
 
 class AddedDiagOperator(LinearOperator):
