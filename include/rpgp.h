@@ -652,6 +652,30 @@ int rpgp_radial_bilinear_grad(int kind, const float *Z, const float *L, const fl
                               void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * Inducing-point (SGPR) sums over the training rows (csrc/rpgp_inducing.hip).  Z (N x d, leading dimension ldz) and U (M x d,
+ * ldu) are float32, centred and divided by the lengthscales; Y is N x T float32, contiguous.  k_i = phi_kind(|z_i - u_.|^2) is
+ * the float32 entry of the radial kernels above (same Gram-form distance, same entry bound, no scale).  Every output is float64,
+ * row-major and contiguous.  1 <= d <= 1024, 1 <= M <= 1024, 0 <= T <= 16 (T == 0: Y, g, v may be NULL), any RPGP_KIND_*.
+ *   rpgp_inducing_gram   G[M x M] = sum_i k_i k_i^T (both triangles), g[M x T] = sum_i k_i Y_i^T.  Products of two float32
+ *                        values are exact in float64; the sums are float64 on v_mfma_f64_16x16x4_f64.
+ *   rpgp_inducing_grad   for C (M x M float64, symmetric) and v (M x T float64), i.e. for the function
+ *                        f = sum(C o G) + sum(v o g):  W = 2 K C + Y v^T,  S = W o phi'(d2)  (K C in float64 with C as given),
+ *                            gU[M x d] = 2 sum_i S_ij (u_j - z_i)               = df / dU
+ *                            q[d]      = sum_ij S_ij (z_im - u_jm)^2            (df / d l_m = -(2 / l_m) q_m)
+ *                        S is rounded to float32 once per entry; every sum over the rows is float64.
+ * The rows are walked in slabs: nothing N-sized is held or written.  The slab length is taken from the workspace handed in:
+ * rpgp_inducing_workspace_bytes(M, d, T, rows) is the size for slabs of `rows` rows (rounded up to 64); any size from
+ * rows = 64 up is accepted and more bytes mean longer slabs; RPGP_EWORKSPACE if smaller.  The size does not depend on N.
+ * Fixed summation order for one slab length, no atomics: repeated calls are bit-identical.  RPGP_EINVAL as above.
+ */
+size_t rpgp_inducing_workspace_bytes(int64_t M, int d, int T, int64_t rows);
+int rpgp_inducing_gram(int kind, const float *Z, const float *U, const float *Y, double *G, double *g, int64_t N, int64_t M,
+                       int d, int ldz, int ldu, int T, void *workspace, size_t workspace_bytes, void *stream);
+int rpgp_inducing_grad(int kind, const float *Z, const float *U, const float *Y, const double *C, const double *v, double *gU,
+                       double *q, int64_t N, int64_t M, int d, int ldz, int ldu, int T, void *workspace,
+                       size_t workspace_bytes, void *stream);
+
+/*
  * Native mBCG executor (replaces gpytorch.utils.linear_cg as configured at gp_experiment_runner.py:324-329; algorithm in
  * SURVEY.md Appendix B.2).  Solves (A) X = rhs for T <= 16 right-hand sides with A described by `rpgp_operator`
  * (noise included), optional Woodbury preconditioner M = L L^T + sigma2 I given as L (N x k, k <= 16) and

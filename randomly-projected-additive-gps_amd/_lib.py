@@ -131,6 +131,9 @@ SIGNATURES = {
     "rpgp_radial_dense": (_int, [_int, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _i64, _f32, _vp, _sz, _vp]),
     "rpgp_radial_bilinear_grad": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _i64, _f32, _vp, _sz,
                                          _vp]),
+    "rpgp_inducing_workspace_bytes": (_sz, [_i64, _int, _int, _i64]),
+    "rpgp_inducing_gram": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _sz, _vp]),
+    "rpgp_inducing_grad": (_int, [_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _int, _int, _vp, _sz, _vp]),
     "rpgp_ski_bilinear_grad_comp": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _int, _int, _int, _int, _int, _f32, _vp,
                                            _sz, _vp, _vp]),
     "rpgp_mbcg_workspace_bytes": (_sz, [_vp, _int, _int]),

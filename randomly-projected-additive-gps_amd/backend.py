@@ -60,6 +60,9 @@ class HipBackend:
     radial_bilinear_grad = staticmethod(ops.radial_bilinear_grad)
     radial_bilinear_grad_dense = staticmethod(ops.radial_bilinear_grad_dense)
     radial_max_dims = ops.RADIAL_MAX_DIMS
+    inducing_gram = staticmethod(ops.inducing_gram)
+    inducing_grad = staticmethod(ops.inducing_grad)
+    inducing_max_points = ops.INDUCING_MAX_POINTS
     gram_f64 = staticmethod(ops.gram_f64)
     woodbury_apply = staticmethod(ops.woodbury_apply)
     woodbury_setup = staticmethod(ops.woodbury_setup)

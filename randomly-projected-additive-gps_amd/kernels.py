@@ -430,6 +430,77 @@ class ScaleKernel(Kernel):
         return f(x1, x2, self.outputscale)
 
 
+class InducingPointKernel(Kernel):
+    """`gpytorch.kernels.InducingPointKernel(base_kernel, inducing_points, likelihood)` of training_routines.py:296-322 for
+    `kind: sgpr`: a trainable M x d set of inducing points initialised by the caller (the first M training rows) around a
+    stationary base kernel (RBF / Matern / InverseMQ, ARD or one lengthscale).  `forward` on the training inputs returns an
+    sgpr.InducingPointOperator: the collapsed bound and the closed-form prediction live in sgpr.py."""
+
+    # why the inducing-point sums of the backend did not serve the last forward() — "settings.sgpr_native is off" included; None
+    # once a forward() was served (and before the first call)
+    sgpr_reason = None
+
+    def __init__(self, base_kernel, inducing_points, likelihood=None):
+        super().__init__()
+        if getattr(base_kernel, "kernel_type", None) not in ("RBF", "Matern", "InverseMQ"):
+            raise ValueError("Unknown kernel type")
+        self.base_kernel = base_kernel
+        self.kernel_type = base_kernel.kernel_type
+        self.inducing_points = nn.Parameter(inducing_points.detach().clone().reshape(-1, inducing_points.shape[-1]))
+        # (held as GPyTorch's kernel holds it; a plain attribute, so that the likelihood's parameters are registered once)
+        object.__setattr__(self, "likelihood", likelihood)
+
+    def center(self, x):
+        """mu: the column mean of the first inputs this kernel saw (the training inputs), detached, once per model — as
+        RBFKernel does for the radial kernels (the kernel is translation-invariant; the Gram form's error grows with the norms)."""
+        mu = getattr(self, "_center", None)
+        if mu is None or mu.shape[0] != x.shape[1] or mu.device != x.device or mu.dtype != x.dtype:
+            mu = self._center = x.detach().mean(dim=0)
+        return mu
+
+    def coordinates(self, x):
+        """(lengthscale, x - mu [detached], U = (inducing_points - mu) / lengthscale [autograd])."""
+        mu = self.center(x)
+        ls = self.base_kernel.lengthscale
+        return ls, x.detach() - mu, (self.inducing_points - mu) / ls
+
+    def _sgpr_reason(self, x):
+        """None when the backend's inducing-point sums serve the objective on x under settings.sgpr_native, else why not."""
+        from . import settings
+        if settings.sgpr_native.off():
+            return "settings.sgpr_native is off"
+        be = _backend.get_backend()
+        if not all(hasattr(be, n) for n in ("inducing_gram", "inducing_grad")):
+            return "the backend has no inducing-point entries"
+        if x.dtype != torch.float32 or self.inducing_points.dtype != torch.float32 or \
+                self.base_kernel.raw_lengthscale.dtype != torch.float32:
+            return "float64 inputs (--double): the inducing-point sums take float32"
+        if getattr(be, "name", "") == "hip-gfx950" and not (x.is_cuda and self.inducing_points.is_cuda):
+            return "host tensors: the inducing-point sums run on the device"
+        if x.dim() != 2 or x.shape[1] != self.inducing_points.shape[1]:
+            return "inputs are not an N x d matrix with the inducing points' d"
+        if x.shape[1] > getattr(be, "radial_max_dims", 1024):
+            return "d = %d is above the %d columns the inducing-point sums take" % (x.shape[1],
+                                                                                  getattr(be, "radial_max_dims", 1024))
+        if self.inducing_points.shape[0] > getattr(be, "inducing_max_points", 1024):
+            return "M = %d is above the %d inducing points the sums take" % (self.inducing_points.shape[0],
+                                                                           getattr(be, "inducing_max_points", 1024))
+        return None
+
+    def forward(self, x1, x2, outputscale=None, **params):
+        from .distributed import is_distributed
+        from .sgpr import InducingPointOperator
+        if is_distributed():
+            raise NotImplementedError("kind sgpr under a process group of more than one rank: the inducing-point sums are not "
+                                      "sharded")
+        same = x2 is None or x2 is x1 or (x1.shape == x2.shape and x1.data_ptr() == x2.data_ptr())
+        if not same:
+            raise NotImplementedError("the inducing-point kernel is evaluated through its objective and its closed-form "
+                                      "prediction (sgpr.py), not as a cross-covariance operator")
+        self.sgpr_reason = reason = self._sgpr_reason(x1)
+        return InducingPointOperator(self, x1, outputscale, reason)
+
+
 class RBFKernel(Kernel):
     """Plain (non-additive) stationary kernel for `kind: full` (training_routines.py:275-293; BASELINE config 1 = CPU
     plumbing through the runner).  NOT the hot path: dense torch ops, any device.  `kernel_type` selects the reference's

@@ -15,6 +15,7 @@ from .hostvals import host_float, prefetch
 from .linear_cg import linear_cg
 from .operators import AddedDiagOperator, AdditiveRPOperator, DenseOperator, SKIAdditiveOperator, SymCachedOperator
 from .precond import build_preconditioner
+from .sgpr import InducingPointOperator, InducingPosterior, InducingPredictive
 
 
 def lanczos_inverse_root(matmul, init_vec, rank):
@@ -60,6 +61,12 @@ class PredictionStrategy:
             self.op = model.covar_module(x)                        # train-train operator
             self.noise = model.likelihood.noise.reshape(()).detach()
             self.r = (y - self.mean_const).reshape(-1, 1)
+            # kind sgpr: the closed-form prediction from the factors of the collapsed bound (sgpr.py); nothing below applies
+            self.sgpr = None
+            if isinstance(self.op, InducingPointOperator):
+                self.lowrank, self.lowrank_fallback_reason = None, "an inducing-point model"
+                self.sgpr = InducingPosterior(self)
+                return
             # settings.lowrank_posterior: the closed-form posterior of the explicit low-rank features where it is served
             # (lowrank_posterior.py); no caches, preconditioner, CG or refinement are built unless a call falls back
             self.lowrank = None
@@ -413,6 +420,8 @@ class PredictionStrategy:
         model = self.model
         at_train = xs is model.train_inputs or (xs.shape == model.train_inputs.shape and
                                                 xs.data_ptr() == model.train_inputs.data_ptr())
+        if self.sgpr is not None:
+            return self.sgpr.predict(xs)
         if self.lowrank is not None:
             out = self._lowrank_predict(xs, at_train)
             if out is not None:
@@ -690,7 +699,7 @@ class ExactMarginalLogLikelihood(nn.Module):
             if output._model is self.model and self.likelihood is self.model.likelihood and settings.fused_training.on():
                 return fused_mll.evaluate(self.model, self.likelihood, target)
         noise = self.likelihood.noise.reshape(())
-        if isinstance(output, TrainPosterior):
+        if isinstance(output, (TrainPosterior, InducingPredictive)):
             res = self.likelihood(output).log_prob(target) + self.likelihood.log_prior().to(target.dtype)
             return res / n
         cov = output.covariance
@@ -700,6 +709,9 @@ class ExactMarginalLogLikelihood(nn.Module):
             prefetch(cov.outputscale, noise)
             inv_quad, logdet = inv_quad_logdet(cov, noise, r)
             log_prob = -0.5 * (inv_quad + logdet + n * LOG2PI)
+        elif isinstance(cov, InducingPointOperator):
+            # kind sgpr: Titsias' collapsed bound in place of the exact marginal likelihood (sgpr.py)
+            log_prob = cov.log_prob(noise, target, output.mean)
         elif isinstance(cov, DenseKernelOperator):
             K = cov.to_dense_autograd() + noise * torch.eye(n, dtype=target.dtype, device=target.device)
             log_prob = _DenseGaussianLogProb.apply(K, target - output.mean)

@@ -1728,6 +1728,82 @@ def radial_bilinear_grad_dense(kind, Z, S, scale):
     return gZ, gs.reshape(())
 
 
+# ------------------------------------------------------------------------------------ inducing-point (SGPR) sums
+
+INDUCING_MAX_POINTS = 1024
+INDUCING_MAX_WIDTH = 16
+INDUCING_WORKSPACE_CAP = 64 << 20
+
+
+def _inducing_args(Z, U, Y):
+    Z = _require(Z, "Z", 2)
+    U = _require(U, "U", 2)
+    N, d = Z.shape
+    M = U.shape[0]
+    if U.shape[1] != d:
+        raise ValueError("Z and U must have the same number of columns")
+    if Y is None:
+        Y = torch.empty((N, 0), dtype=torch.float32, device=Z.device)
+    Y, _ = _as_matrix(Y, N, "Y")
+    if Y.device != Z.device or U.device != Z.device:
+        raise ValueError("Z, U and Y must live on one device")
+    return Z, U, Y, N, M, d, Y.shape[1]
+
+
+def _inducing_workspace(lib, device, N, M, d, T, rows):
+    """(buffer, bytes handed to the entry).  The entry takes its slab length from the BYTES: the size asked for is passed on, not
+    the size of the (grow-only) buffer, so that one call's slabs do not depend on what ran before it.  `rows` None: slabs as
+    long as INDUCING_WORKSPACE_CAP allows, at most N rows."""
+    floor = lib.rpgp_inducing_workspace_bytes(M, d, T, 64)
+    if floor == 0:
+        raise ValueError("inducing sums: 1 <= M <= %d, 1 <= d <= %d and T <= %d required (got M = %d, d = %d, T = %d)"
+                         % (INDUCING_MAX_POINTS, RADIAL_MAX_DIMS, INDUCING_MAX_WIDTH, M, d, T))
+    if rows is None:
+        nbytes = max(floor, min(lib.rpgp_inducing_workspace_bytes(M, d, T, N), INDUCING_WORKSPACE_CAP))
+    else:
+        nbytes = lib.rpgp_inducing_workspace_bytes(M, d, T, int(rows))
+    return _workspace(device, nbytes), nbytes
+
+
+def inducing_gram(kind, Z, U, Y=None, rows=None):
+    """(G [M x M], g [M x T]) in float64: G = sum_i k_i k_i^T, g = sum_i k_i Y_i^T with k_i = phi_kind(|z_i - u_.|^2) the float32
+    entries of the radial kernels (rpgp_inducing_gram).  Z: N x d, U: M x d, Y: N x T (T <= 16) or None.  `rows`: slab length
+    of the workspace (tests); no N x M object is held."""
+    lib = _lib.load()
+    Z, U, Y, N, M, d, T = _inducing_args(Z, U, Y)
+    G = torch.empty((M, M), dtype=torch.float64, device=Z.device)
+    g = torch.empty((M, T), dtype=torch.float64, device=Z.device)
+    with _on(Z.device):
+        ws, nbytes = _inducing_workspace(lib, Z.device, N, M, d, T, rows)
+        _lib.check(lib.rpgp_inducing_gram(_radial_kind(kind), Z.data_ptr(), U.data_ptr(), Y.data_ptr() if T else None,
+                                          G.data_ptr(), g.data_ptr() if T else None, N, M, d, d, d, T, ws.data_ptr(), nbytes,
+                                          _stream()), "rpgp_inducing_gram")
+    return G, g
+
+
+def inducing_grad(kind, Z, U, Y, C, v, rows=None):
+    """(gU [M x d], q [d]) in float64 for f = sum(C o G) + sum(v o g) of inducing_gram: gU = df / dU and
+    q_m = sum_ij S_ij (z_im - u_jm)^2 with S = (2 K C + Y v^T) o phi' (rpgp_inducing_grad).  C: M x M float64, symmetric;
+    v: M x T float64 (None with Y None)."""
+    lib = _lib.load()
+    Z, U, Y, N, M, d, T = _inducing_args(Z, U, Y)
+    if C.dtype != torch.float64 or tuple(C.shape) != (M, M) or C.device != Z.device:
+        raise ValueError("C must be an M x M float64 tensor on the device of Z")
+    C = C.contiguous()
+    if T:
+        if v is None or v.dtype != torch.float64 or tuple(v.shape) != (M, T) or v.device != Z.device:
+            raise ValueError("v must be an M x T float64 tensor on the device of Z")
+        v = v.contiguous()
+    gU = torch.empty((M, d), dtype=torch.float64, device=Z.device)
+    q = torch.empty((d,), dtype=torch.float64, device=Z.device)
+    with _on(Z.device):
+        ws, nbytes = _inducing_workspace(lib, Z.device, N, M, d, T, rows)
+        _lib.check(lib.rpgp_inducing_grad(_radial_kind(kind), Z.data_ptr(), U.data_ptr(), Y.data_ptr() if T else None,
+                                          C.data_ptr(), v.data_ptr() if T else None, gU.data_ptr(), q.data_ptr(), N, M, d, d,
+                                          d, T, ws.data_ptr(), nbytes, _stream()), "rpgp_inducing_grad")
+    return gU, q
+
+
 def make_operator_desc(kind, N, J, scale, noise, Z=None, prep=None, gp=None, j0=0, j1=None, G=0, Kd=None, family=None,
                        symcache=None, world=1, rank=0, lowrank=None):
     """Fill a `struct rpgp_operator`; returns (struct, keepalive) — keep both referenced while the solve runs.

@@ -155,6 +155,12 @@ lowrank_panels = _setting("lowrank_panels", False, flag=True)
 # entries; anything else keeps the dense torch operator (RBFKernel.fused_full_reason says why).  Off (the default): every path
 # is the dense one, bit for bit.  DESIGN.md 7.10.
 fused_full = _setting("fused_full", False, flag=True)
+# `kind: sgpr` (kernels.InducingPointKernel, sgpr.py): the collapsed bound through the inducing-point sums of
+# csrc/rpgp_inducing.hip (no N x M object) for float32 device tensors, d <= 1024, M <= 1024, one rank.  Off, or where that is
+# not served (InducingPointKernel.sgpr_reason says why): the same objective through a dense N x M block in float64 on any device
+# and dtype.  sgpr_jitter is added to the diagonal of K_uu always (the objective is smooth and deterministic).  DESIGN.md 7.12.
+sgpr_native = _setting("sgpr_native", True, flag=True)
+sgpr_jitter = _setting("sgpr_jitter", 1e-6)
 # prediction through the explicit features of the same low-rank form (lowrank_posterior.py): an unsharded additive-RP RBF model
 # with a float64 twin (k = 1, no grid), J <= 64, Chebyshev rank p <= lowrank_max_rank (64 by default, up to 128), at most 4096
 # features in 25 % of the device memory gets its posterior mean, covariance, log-densities and solves in closed form in float64 (F x F factorisations, no N x N object, no CG).  Off, or

@@ -62,6 +62,8 @@ SPECS = {
     "additive_deterministic_spec_unweighted": _spec("strictly_additive", noise_prior=True, kernel_type="RBF", weighted=False),
     "ARD_RO": _spec("full", train=dict(_ADAM, checkpoint=True, random_restarts=10), noise_prior=True, kernel_type="RBF",
                     ard=True, init_lengthscale_range=[0.4, 0.8]),
+    # the sparse baseline: inducing-point GP on Titsias' collapsed bound (sgpr.py)
+    "SGPR_ARD_model_spec": _spec("sgpr", noise_prior=True, kernel_type="RBF", ard=True, inducing_points=400),
     # multiplicative groups of different sizes (operators.MixedGroupOperator)
     "polynomial_rp": _spec("general_rp_poly", degrees=[1, 1, 1, 2, 2, 2, 3, 3, 3, 4, 4, 5, 5, 6], noise_prior=True,
                            kernel_type="RBF", learn_proj=False, weighted=True),

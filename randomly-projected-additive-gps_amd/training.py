@@ -12,15 +12,15 @@ import torch.distributed as dist
 
 from . import rp
 from .distributed import JShard, RowShard, is_distributed
-from .kernels import (AdditiveStructureRBFKernel, CustomAdditiveKernel, MemoryEfficientGamKernel,
+from .kernels import (AdditiveStructureRBFKernel, CustomAdditiveKernel, InducingPointKernel, MemoryEfficientGamKernel,
                       PolynomialProjectionKernel, RBFKernel, ScaledProjectionKernel, ScaleKernel, StrictlyAdditiveKernel)
 from .likelihoods import GaussianLikelihood, SmoothedBoxPrior
 from .models import ExactGPModel, ExactMarginalLogLikelihood
 from .ops import trace_range
 from . import fused_mll
 
-EXACT_GP_KINDS = ("full", "additive_rp", "strictly_additive", "additive", "rp_poly", "general_rp_poly")
-REFERENCE_ONLY_KINDS = ("rp", "deep_rp_poly", "multi_full", "duvenaud_additive", "sgpr")
+EXACT_GP_KINDS = ("full", "additive_rp", "strictly_additive", "additive", "rp_poly", "general_rp_poly", "sgpr")
+REFERENCE_ONLY_KINDS = ("rp", "deep_rp_poly", "multi_full", "duvenaud_additive")
 
 
 def _map_to_optim(optimizer):
@@ -205,6 +205,21 @@ def create_full_kernel(d, ard=False, ski=False, grid_size=None, kernel_type="RBF
     return kernel
 
 
+def create_sgpr_kernel(d, ard=False, kernel_type="RBF", inducing_points=800, init_lengthscale_range=(1.0, 1.0), X=None,
+                       likelihood=None):
+    """Inducing-point kernel for `kind: sgpr` (training_routines.py:296-322): a stationary base kernel around the first
+    `inducing_points` rows of X (all of X when there are fewer), trainable.  Cosine is an unknown type here, as there."""
+    if kernel_type not in ("RBF", "Matern", "InverseMQ"):
+        raise ValueError("Unknown kernel type")
+    kernel = RBFKernel(ard_num_dims=d if ard else None, kernel_type=kernel_type)
+    kernel.initialize(lengthscale=_sample_from_range(d if ard else 1, init_lengthscale_range))
+    if X is None:
+        raise ValueError("X is required")
+    if likelihood is None:
+        raise ValueError("Likelihood is required")
+    return InducingPointKernel(kernel, X[:inducing_points], likelihood)
+
+
 def create_exact_gp(trainX, trainY, kind, devices=("cpu",), **kwargs):
     """Create an exact GP model with a specified kernel (training_routines.py:325-410).
     Under a torch.distributed process group (one process per GPU) the exact additive_rp kernel is pair- / J-sharded
@@ -233,6 +248,8 @@ def create_exact_gp(trainX, trainY, kind, devices=("cpu",), **kwargs):
         kernel = create_rp_poly_kernel(d, X=trainX, **kwargs)
     elif kind == "general_rp_poly":
         kernel = create_general_rp_poly_kernel(d, X=trainX, **kwargs)
+    elif kind == "sgpr":
+        kernel = create_sgpr_kernel(d, X=trainX, likelihood=likelihood, **kwargs)
     else:
         kernel = create_additive_rp_kernel(d, **kwargs)
     kernel = ScaleKernel(kernel)
