@@ -98,7 +98,10 @@ def test_bench_plain_run_times_the_steps_and_dumps_the_last_product(gpu_device, 
     res = json.loads(lines[0])
     assert res["n_gpus"] == 1 and res["steps"] == 7 and res["warmup"] == 1 and res["unit"] == "MVM/s"
     assert res["higher_is_better"] is True and res["dtype"] == "f32" and res["metric"].startswith("additive-RP kernel MVMs/sec")
-    assert res["value"] > 0 and abs(res["value"] * res["ms_per_step"] / 1e3 - 1.0) < 1e-3
+    # value = steps / elapsed and ms_per_step = 1e3 elapsed / steps are printed rounded to 3 and to 4 decimals: they agree to
+    # half a unit of ms_per_step's last decimal (a step at this size is ~0.026 ms, where that half unit is 2e-3 relative: a
+    # relative 1e-3 held or not by the luck of the rounding; above 0.05 ms this is the tighter statement)
+    assert res["value"] > 0 and abs(res["ms_per_step"] - 1e3 / res["value"]) <= 0.5e-4 + 1e-7
     assert not {"extras", "cpu_baseline", "cpu_baseline_best", "prepare_us", "multi_gpu"} & set(res)
     assert sorted(os.listdir(out_dir)) == ["mvm_out.npy"]
     out = np.load(out_dir / "mvm_out.npy")

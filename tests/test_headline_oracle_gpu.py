@@ -3,9 +3,10 @@ seeds).  Three 256-row blocks of  K[rows, :] @ V + sigma^2 V[rows]  — first, m
 boundary) and last (the ragged tail: 50 000 = 97 * 512 + 336) — plus a seeded random sample of 256 rows spread over
 every row-block class (so that no interior tile can be wrong unseen) are evaluated in FLOAT64 numpy from the reference's
 formula (gp_models/kernels/memory_efficient_gam_kernel.py:20-30: sum_j exp(-0.5 (z_ij - z_i'j)^2)) and every product on the
-path is compared with them through the C-ABI: the prepared kernel `mvm_fact_kernel` (T = 1: the benchmark's launch, and
-the T = 11 training block), the direct kernel, the packed symmetric cache in both layouts, the dense cached-K stream, and
-a pair-sharded sum.  Tolerance 1e-5 relative (2-norm per column) — the bound north_star states is 1e-4.
+path is compared with them through the C-ABI: the prepared product as ops.mvm_sym_prepared serves it (the Chebyshev low-rank
+form, rpgp_mvm_sym_lowrank_range: T = 1, the benchmark's launch, and the T = 11 training block) and, inside sweep(), the exact
+prepared sweep (`mvm_fact_kernel`, hand-scheduled and compiler-scheduled at T = 1), the direct kernel, the packed symmetric
+cache in both layouts, the dense cached-K stream, and a pair-sharded sum.  Tolerance 1e-5 relative (2-norm per column) — the bound north_star states is 1e-4.
 The bilinear derivative (memory_efficient_gam_kernel.py:33-59) is checked on 64 rows of gZ."""
 import math
 
@@ -65,26 +66,43 @@ def _check(out, refs, cols, what):
 
 
 def test_prepared_kernel_bench_launch_t1_and_t11(c4):
-    """`ops.mvm_sym_prepared` = mvm_fact_kernel<20, 1, 2> at T = 1 (exactly what bench.py launches) and the T = 11 block."""
+    """`ops.mvm_sym_prepared` at T = 1 (exactly what bench.py launches) and the T = 11 block.  By itself the call reaches
+    rpgp_mvm_sym_lowrank_range (this Z has a low-rank plan).  Inside sweep() it reaches the exact sweep: at T = 1 the
+    hand-scheduled form of mvm_fact_kernel<20, 1, 2> (RPGP_FACT_ASM=1, rpgp_fact_asm.hip, tapered plan) and the
+    compiler-scheduled mvm_fact_kernel<20, 1, 2> itself (RPGP_FACT_ASM=0), at T = 11 mvm_fact_kernel<20, 12, 2>."""
     from rpgp_amd import ops
+    from tests.prepared_sweep_reference import sweep
     prep = ops.Prepared(c4["Z"])
     assert prep.fast_ok
     V = c4["V"]
-    _check(ops.mvm_sym_prepared(prep, V[:, :1].contiguous(), SCALE, NOISE), c4["refs"], slice(0, 1), "prepared T=1")
+    V1 = V[:, :1].contiguous()
+    _check(ops.mvm_sym_prepared(prep, V1, SCALE, NOISE), c4["refs"], slice(0, 1), "prepared T=1")
     _check(ops.mvm_sym_prepared(prep, V, SCALE, NOISE), c4["refs"], slice(0, 11), "prepared T=11")
+    for env_asm in ("1", "0"):
+        with sweep(env_asm):
+            _check(ops.mvm_sym_prepared(prep, V1, SCALE, NOISE), c4["refs"], slice(0, 1), "sweep T=1 asm=" + env_asm)
+    with sweep():
+        _check(ops.mvm_sym_prepared(prep, V, SCALE, NOISE), c4["refs"], slice(0, 11), "sweep T=11")
 
 
 def test_bench_launch_every_row_against_the_c_oracle(c4):
     """ALL 50 000 output rows of the benchmark's launch against the float64 C/OpenMP restatement (oracle/cmvm.c: the full
     2.5e9-entry kernel matrix, 5e10 exponentials — seconds on the GPU box's host cores): no tile of the decomposition is
-    left unchecked."""
+    left unchecked.  The launch is rpgp_mvm_sym_lowrank_range; the same reference then holds the exact sweep
+    (rpgp_mvm_sym_prepared_range inside sweep()): the hand-scheduled kernel and the compiler-scheduled mvm_fact_kernel<20, 1, 2>."""
     from oracle import cmvm
     from rpgp_amd import ops
+    from tests.prepared_sweep_reference import sweep
     ref = cmvm.mvm(c4["Zh"], c4["Zh"], c4["Vh"][:, :1], SCALE, NOISE)
     prep = ops.Prepared(c4["Z"])
     out = ops.mvm_sym_prepared(prep, c4["V"][:, :1].contiguous(), SCALE, NOISE).double().cpu().numpy()
     assert np.linalg.norm(out - ref) / np.linalg.norm(ref) < 1e-5
     assert np.abs(out - ref).max() < 1e-5 * np.abs(ref).max()
+    for env_asm in ("1", "0"):
+        with sweep(env_asm):
+            out_s = ops.mvm_sym_prepared(prep, c4["V"][:, :1].contiguous(), SCALE, NOISE).double().cpu().numpy()
+        assert np.linalg.norm(out_s - ref) / np.linalg.norm(ref) < 1e-5, env_asm
+        assert np.abs(out_s - ref).max() < 1e-5 * np.abs(ref).max(), env_asm
     # ... and the row subsets used by the other tests are the same numbers the numpy formula gives
     for rows, r in c4["refs"]:
         assert np.abs(ref[rows] - r[:, :1]).max() < 1e-11 * np.abs(r).max()
@@ -98,7 +116,8 @@ def test_direct_kernel_t1_and_t11(c4):
 
 
 def test_pair_sharded_partials_sum_to_the_oracle(c4):
-    """Three emulated ranks (prepared kernel, noise on rank 0 only): the sum of the partial products is the oracle's."""
+    """Three emulated ranks (ops.mvm_sym_prepared, which serves rpgp_mvm_sym_lowrank_range here; noise on rank 0 only): the sum
+    of the partial products is the oracle's."""
     from rpgp_amd import ops
     prep = ops.Prepared(c4["Z"])
     V1 = c4["V"][:, :1].contiguous()

@@ -298,12 +298,21 @@ def test_bilinear_grad_dense_matches_oracle(gpu_device, N, J):
     assert abs(gs.item() - gs_ref) < 2e-4 * np.abs(s * ks).sum() * 0.5 / N + 2e-5 * abs(gs_ref)
 
 
-@pytest.mark.parametrize("N,J,T,shift", [(63, 20, 1, 0.0), (1000, 20, 1, 5.0), (777, 18, 4, -3.0), (2049, 8, 1, 100.0),
-                                         (1500, 7, 13, 0.0), (4096, 20, 11, 1.0), (300, 3, 1, 0.0), (16500, 20, 1, 0.5)])
-def test_mvm_sym_prepared_matches_oracle(gpu_device, N, J, T, shift):
-    """Factorised fast path (rpgp_prepare + rpgp_mvm_sym_prepared): same contract as rpgp_mvm_sym; the centring makes
-    it invariant to a common shift of the projected coordinates."""
+_PREPARED_CASES = [(63, 20, 1, 0.0), (1000, 20, 1, 5.0), (777, 18, 4, -3.0), (2049, 8, 1, 100.0),
+                   (1500, 7, 13, 0.0), (4096, 20, 11, 1.0), (300, 3, 1, 0.0), (16500, 20, 1, 0.5)]
+
+
+@pytest.mark.parametrize("N,J,T,shift,path",
+                         [pytest.param(*c, "default", id="-".join(str(x) for x in c)) for c in _PREPARED_CASES] +
+                         [pytest.param(*c, "sweep", id="-".join(str(x) for x in c) + "-sweep") for c in _PREPARED_CASES])
+def test_mvm_sym_prepared_matches_oracle(gpu_device, N, J, T, shift, path):
+    """ops.mvm_sym_prepared (rpgp_prepare + the prepared product): same contract as rpgp_mvm_sym; the centring makes it
+    invariant to a common shift of the projected coordinates.  path "default": what the call serves by itself — every Z here
+    has a low-rank plan, so rpgp_mvm_sym_lowrank_range.  path "sweep": the exact factorised sweep
+    (rpgp_mvm_sym_prepared_range, RPGP_LOWRANK=0) over the same J pieces, T blocks and ragged N, against the same oracle."""
+    import contextlib
     from rpgp_amd import ops
+    from tests.prepared_sweep_reference import sweep
     Z, V = _data(N, J, T, seed=N + J + 1)
     Z = (Z + np.float32(shift)).astype(np.float32)
     scale, noise = 0.7 / J, 0.1
@@ -311,9 +320,10 @@ def test_mvm_sym_prepared_matches_oracle(gpu_device, N, J, T, shift):
     Zt = torch.from_numpy(Z).to(gpu_device)
     prep = ops.Prepared(Zt)
     assert prep.fast_ok and prep.max_abs < 10.0
-    out = ops.mvm_sym_prepared(prep, torch.from_numpy(V).to(gpu_device), scale, noise)
-    assert _rel(out.cpu().numpy(), ref) < 1e-5
-    part = ops.mvm_sym_prepared(prep, torch.from_numpy(V).to(gpu_device), scale, 0.0, j0=1, j1=J)
+    with (sweep() if path == "sweep" else contextlib.nullcontext()):
+        out = ops.mvm_sym_prepared(prep, torch.from_numpy(V).to(gpu_device), scale, noise)
+        assert _rel(out.cpu().numpy(), ref) < 1e-5
+        part = ops.mvm_sym_prepared(prep, torch.from_numpy(V).to(gpu_device), scale, 0.0, j0=1, j1=J)
     ref_p = omvm(Z[:, 1:], Z[:, 1:], V, scale) if J > 1 else None
     if ref_p is not None:
         assert _rel(part.cpu().numpy(), ref_p) < 1e-5
@@ -393,9 +403,12 @@ def test_pivoted_cholesky_step_kernels_on_both_sides_of_their_limits(gpu_device,
 
 @pytest.mark.parametrize("N,T,world", [(3000, 1, 3), (20000, 1, 8), (5000, 11, 4), (700, 4, 2), (300, 1, 8)])
 def test_pair_sharded_mvm_sums_to_full(gpu_device, N, T, world):
-    """Pair-sharding (rpgp_mvm_sym[_prepared]_range): the per-rank partial products sum to the full MVM, for the
-    direct and the prepared kernels, including j-ranges."""
+    """Pair-sharding: the per-rank partial products sum to the full MVM, including j-ranges — for the direct kernels
+    (rpgp_mvm_sym_range), for what ops.mvm_sym_prepared serves by itself (these Z have a low-rank plan:
+    rpgp_mvm_sym_lowrank_range) and, inside sweep(), for the exact prepared sweep (rpgp_mvm_sym_prepared_range), which is what
+    a pair-sharded multi-GPU run launches."""
     from rpgp_amd import ops
+    from tests.prepared_sweep_reference import sweep
     Z, V = _data(N, 20, T, seed=N)
     Zt, Vt = torch.from_numpy(Z).to(gpu_device), torch.from_numpy(V).to(gpu_device)
     full = ops.mvm_sym(Zt, Vt, 0.05, 0.0)
@@ -406,6 +419,11 @@ def test_pair_sharded_mvm_sums_to_full(gpu_device, N, T, world):
     assert _rel(acc_p.cpu().numpy(), full.cpu().numpy()) < 2e-6
     part = sum(ops.mvm_sym_prepared(prep, Vt, 0.05, 0.0, j0=3, j1=11, shard=(world, r)) for r in range(world))
     assert _rel(part.cpu().numpy(), ops.mvm_sym(Zt, Vt, 0.05, 0.0, j0=3, j1=11).cpu().numpy()) < 2e-6
+    with sweep():
+        acc_s = sum(ops.mvm_sym_prepared(prep, Vt, 0.05, 0.0, shard=(world, r)) for r in range(world))
+        part_s = sum(ops.mvm_sym_prepared(prep, Vt, 0.05, 0.0, j0=3, j1=11, shard=(world, r)) for r in range(world))
+    assert _rel(acc_s.cpu().numpy(), full.cpu().numpy()) < 2e-6
+    assert _rel(part_s.cpu().numpy(), ops.mvm_sym(Zt, Vt, 0.05, 0.0, j0=3, j1=11).cpu().numpy()) < 2e-6
 
 
 def test_edge_shapes(gpu_device):
