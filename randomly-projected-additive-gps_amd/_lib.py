@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/rpgp.h (librpgp.so, built from csrc/rpgp_kernels.hip).
+"""ctypes binding of the C-ABI in include/rpgp.h (librpgp.so, built from csrc/*.hip: one object per source).
 
 There is NO fallback: if the shared library is missing or a call fails, an exception is raised.
 """

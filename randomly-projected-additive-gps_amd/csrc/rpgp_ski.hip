@@ -31,7 +31,7 @@
 namespace {
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int launch_status() { return (int)hipGetLastError(); }
+using rpgp_internal::launch_status;
 
 // ---- plan layout -------------------------------------------------------------------------------------------------------
 struct PlanView {

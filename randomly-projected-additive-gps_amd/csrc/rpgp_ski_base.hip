@@ -19,13 +19,8 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 __device__ __forceinline__ float min_nan(float a, float b) { return (a != a) ? a : ((b != b) ? b : (b < a ? b : a)); }
 __device__ __forceinline__ float max_nan(float a, float b) { return (a != a) ? a : ((b != b) ? b : (b > a ? b : a)); }
 
-inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
-#define RPGP_CHECK(expr)                          \
-  do {                                            \
-    hipError_t _e = (expr);                       \
-    if (_e != hipSuccess) return (int)_e;         \
-  } while (0)
-inline int launch_status() { return (int)hipGetLastError(); }
+using rpgp_internal::as_stream;
+using rpgp_internal::launch_status;
 
 // ---------------------------------------------------------------------------------------------
 // SKI path (spec additive_spread_prescale_Jd_ski.json):

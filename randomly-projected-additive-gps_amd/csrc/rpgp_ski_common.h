@@ -1,4 +1,4 @@
-// rpgp_ski_common.h — device helpers of the SKI path shared by rpgp_kernels.hip and rpgp_ski.hip (not part of the C-ABI).
+// rpgp_ski_common.h — device helpers of the SKI path shared by rpgp_ski_base.hip, rpgp_ski.hip and rpgp_pivchol.hip (not part of the C-ABI).
 #pragma once
 #include <hip/hip_runtime.h>
 

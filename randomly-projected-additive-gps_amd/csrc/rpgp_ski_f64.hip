@@ -14,10 +14,11 @@
 #include <stdint.h>
 
 #include "../../include/rpgp.h"
+#include "rpgp_internal.h"
 
 namespace {
 
-inline int launch_status() { return (int)hipGetLastError(); }
+using rpgp_internal::launch_status;
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ double cubic_w(double U) {

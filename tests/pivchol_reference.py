@@ -111,7 +111,7 @@ def _phi_sens(kind, r):
 
 
 def _phi_f32(kind, dd):
-    """Phi<kind>::val of the pre-scaled float32 difference dd (csrc/rpgp_kernels.hip)."""
+    """Phi<kind>::val of the pre-scaled float32 difference dd (csrc/rpgp_tile.h)."""
     f = np.float32
     if kind == "RBF":
         return np.exp2(-(dd * dd))

@@ -1,4 +1,4 @@
-"""Every device path of the pivoted-Cholesky factor (csrc/rpgp_kernels.hip, dispatched by pivchol_common) held to float64
+"""Every device path of the pivoted-Cholesky factor (csrc/rpgp_pivchol.hip, dispatched by pivchol_common) held to float64
 one greedy step at a time by tests/pivchol_reference.py: pivot, no repeat, greedy optimality, and every entry of the new
 column within C u B of the float64 column computed from the factor's own earlier columns (C per operator kind: measured on
 the host by tests/test_pivchol_reference_host.py, which also asserts that every main case is resolved).
