@@ -531,6 +531,27 @@ int rpgp_ski_f64_bilinear_finish(const double *Z, const double *grid_params, con
                                  double scale, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
+ * The two passes over the rows of the closed-form posterior of the grid-interpolation models (csrc/rpgp_ski_post.hip;
+ * ski_posterior.py).  w_i: the 4 J cubic-convolution weights of row i of Z (N x J, leading dimension ldz) placed
+ * in a vector of J G entries, by the stencil rule of every SKI entry point (grid coordinate clipped to [1, G - 2], first tap in
+ * [0, G - 4]).  Every array float64; grid_params: the float64 grid block above (both grid rules and the weights flag parse; the
+ * weights and the kind do not enter).  No float atomics, every sum in a fixed order: a repeated call is bit-identical.
+ *   rpgp_ski_gram_f64      A (J G x J G, row-major, both triangles, A == A^T bitwise) = sum_i w_i w_i^T and g (J G x T, row-major)
+ *                          = sum_i w_i Y_i^T for Y (N x T, row-major), 0 <= T <= 16; Y and g may be NULL when T == 0.  Workspace:
+ *                          rpgp_ski_gram_f64_workspace_bytes(N, J, G, T) (0 for a shape that is not served), 16-byte aligned;
+ *                          RPGP_EWORKSPACE if smaller.  RPGP_EINVAL: N outside 1 ... 2^31 - 1, J outside 1 ... 65535, G outside
+ *                          8 ... 8192, T outside 0 ... 16, ldz < J, a null or misaligned pointer.
+ *   rpgp_ski_quadform_f64  out[i] = w_i^T C w_i for the M rows of Z; C: J G x J G with leading dimension ldc >= J G, BOTH
+ *                          triangles are read (the plain double sum over the 4 J x 4 J taps, nothing doubled).  RPGP_EINVAL:
+ *                          M < 1, J outside 1 ... 65535, G < 8, ldz < J, ldc < J G, a null or misaligned pointer.
+ */
+size_t rpgp_ski_gram_f64_workspace_bytes(int64_t N, int J, int G, int T);
+int rpgp_ski_gram_f64(const double *Z, const double *grid_params, const double *Y, double *A, double *g, int64_t N, int ldz, int J,
+                      int G, int T, void *workspace, size_t workspace_bytes, void *stream);
+int rpgp_ski_quadform_f64(const double *Z, const double *grid_params, const double *C, double *out, int64_t M, int ldz, int J,
+                          int G, int64_t ldc, void *stream);
+
+/*
  * The derivative in two stages for the row-sharded SKI operator (MLL backward of a model whose rows are split over ranks):
  *   rpgp_ski_bilinear_scatter : hist2[j][g][0..T) = W_j^T L, hist2[j][g][T..2T) = W_j^T R over the N LOCAL rows (float64,
  *                               J * G * 2T) — all-reduce it over the ranks —

@@ -47,6 +47,8 @@ class HipBackend:
     ski_bilinear_grad_comp = staticmethod(ops.ski_bilinear_grad_comp)
     ski_bilinear_scatter = staticmethod(ops.ski_bilinear_scatter)
     ski_bilinear_finish = staticmethod(ops.ski_bilinear_finish)
+    ski_gram = staticmethod(ops.ski_gram)
+    ski_quadform = staticmethod(ops.ski_quadform)
     make_family = staticmethod(ops.Family)
     family_mvm_sym = staticmethod(ops.family_mvm_sym)
     family_mvm_rect = staticmethod(ops.family_mvm_rect)

@@ -63,6 +63,7 @@ class PredictionStrategy:
             self.r = (y - self.mean_const).reshape(-1, 1)
             # kind sgpr: the closed-form prediction from the factors of the collapsed bound (sgpr.py); nothing below applies
             self.sgpr = None
+            self.ski_post, self.ski_posterior_reason = None, None
             if isinstance(self.op, InducingPointOperator):
                 self.lowrank, self.lowrank_fallback_reason = None, "an inducing-point model"
                 self.sgpr = InducingPosterior(self)
@@ -74,6 +75,13 @@ class PredictionStrategy:
             if settings.lowrank_posterior.on():
                 from .lowrank_posterior import LowrankPosterior
                 self.lowrank, self.lowrank_fallback_reason = LowrankPosterior.build(self)
+            # settings.ski_posterior: the closed-form posterior of an unsharded grid-interpolation model from Gram sums over its
+            # grid nodes (ski_posterior.py); consulted before the exact path, like the feature posterior above
+            if settings.ski_posterior.on() and self.lowrank is None and isinstance(self.op, SKIAdditiveOperator):
+                from .ski_posterior import SKIPosterior
+                self.ski_post, self.ski_posterior_reason = SKIPosterior.build(self)
+                if self.ski_post is not None:
+                    return
             if self.lowrank is None:
                 self._init_exact()
 
@@ -269,7 +277,7 @@ class PredictionStrategy:
     def _train_closed_form_ready(self, like):
         """Closed form available: the feature posterior, the dense (Cholesky) regime, or the CG regime where the float32
         factor + float64 copy of the mixed-precision solve exist / fit (settings.solve_refinement on)."""
-        if self.lowrank is not None:
+        if self.lowrank is not None or self.ski_post is not None:
             return True
         if self.dense_path:
             return True
@@ -285,6 +293,8 @@ class PredictionStrategy:
         training_routines.py:567-569 for the train set."""
         if self.lowrank is not None:
             return self.lowrank.train_log_prob(target)
+        if self.ski_post is not None:
+            return self.ski_post.train_log_prob(target)
         N = self.r.shape[0]
         s2 = host_float(self.noise)
         mean = (self.model.train_targets.double().reshape(-1, 1) - s2 *
@@ -426,6 +436,15 @@ class PredictionStrategy:
             out = self._lowrank_predict(xs, at_train)
             if out is not None:
                 return out
+            return self._predict_exact(xs)
+        if self.ski_post is not None:
+            out = self.ski_post.predict(xs, at_train=at_train)
+            if out is not None:
+                return out
+            # (the block that covers xs is not served: today's state from here on, the reason in ski_posterior_reason)
+            self.ski_post = None
+            self.alpha64 = None
+            self._init_exact()
             return self._predict_exact(xs)
         with torch.no_grad():
             if at_train and self._train_closed_form_ready(xs):

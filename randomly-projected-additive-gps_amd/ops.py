@@ -2170,3 +2170,67 @@ def _ski64_bilinear(Z, gp, L, R, scale, grid_size):
             gs += gsp
             gc += gcp
     return gZ, gs, gc
+
+
+# ---- the row passes of the closed-form SKI posterior (csrc/rpgp_ski_post.hip; ski_posterior.py) ---------------------------------
+def _ski_post_rows(Z, gp, name):
+    """Z as float64 rows on the device with unit column stride (a row stride above J is passed on as ldz), and the float64 grid
+    block."""
+    if not isinstance(Z, torch.Tensor) or not isinstance(gp, torch.Tensor):
+        raise TypeError("%s and the grid block must be torch tensors" % name)
+    if not Z.is_cuda or not gp.is_cuda:
+        raise RuntimeError("%s must live on a HIP device (got %s): the rpgp kernels have no CPU fallback" % (name, Z.device))
+    if Z.dtype != torch.float64 or gp.dtype != torch.float64:
+        raise TypeError("%s and the grid block must be float64 (got %s, %s)" % (name, Z.dtype, gp.dtype))
+    if Z.dim() != 2:
+        raise ValueError("%s must be 2-dimensional (got shape %s)" % (name, tuple(Z.shape)))
+    if Z.shape[0] <= 1 or Z.stride(1) != 1 or Z.stride(0) < Z.shape[1]:
+        Z = Z.contiguous()
+    return Z, gp.contiguous()
+
+
+def ski_gram(Z, gp, Y=None, grid_size=1024):
+    """(A, g): A = sum_i w_i w_i^T (J G x J G float64, both triangles, bitwise symmetric) and g = sum_i w_i Y_i^T (J G x T; None
+    without Y) over the rows of Z, w_i the 4 J interpolation weights of row i on the grid block gp (rpgp_ski_gram_f64: no float
+    atomics, a repeated call is bit-identical).  Y: N or N x T float64, T <= 16."""
+    lib = _lib.load()
+    Z, gp = _ski_post_rows(Z, gp, "Z")
+    N, J = Z.shape
+    G = int(grid_size)
+    ldz = Z.stride(0) if N > 1 else J
+    T = 0
+    Y2 = g = None
+    if Y is not None:
+        Y2 = Y.reshape(N, -1).contiguous()
+        if Y2.dtype != torch.float64 or Y2.device != Z.device:
+            raise TypeError("Y must be float64 on the device of Z")
+        T = Y2.shape[1]
+        g = torch.empty((J * G, T), dtype=torch.float64, device=Z.device)
+    need = lib.rpgp_ski_gram_f64_workspace_bytes(N, J, G, T)
+    if need == 0:
+        raise ValueError("rpgp_ski_gram_f64: shape not served (N = %d, J = %d, G = %d, T = %d)" % (N, J, G, T))
+    A = torch.empty((J * G, J * G), dtype=torch.float64, device=Z.device)
+    with _on(Z.device):
+        ws = _workspace(Z.device, need)
+        _lib.check(lib.rpgp_ski_gram_f64(Z.data_ptr(), gp.data_ptr(), None if Y2 is None else Y2.data_ptr(), A.data_ptr(),
+                                         None if g is None else g.data_ptr(), N, ldz, J, G, T, ws.data_ptr(), ws.numel(),
+                                         _stream()), "rpgp_ski_gram_f64")
+    return A, g
+
+
+def ski_quadform(Z, gp, C, grid_size=1024):
+    """out[i] = w_i^T C w_i (float64) for the rows of Z; C: J G x J G float64, both triangles read (rpgp_ski_quadform_f64)."""
+    lib = _lib.load()
+    Z, gp = _ski_post_rows(Z, gp, "Z")
+    M, J = Z.shape
+    G = int(grid_size)
+    if not isinstance(C, torch.Tensor) or C.dtype != torch.float64 or C.device != Z.device or C.dim() != 2 or \
+            C.shape[0] != J * G or C.shape[1] != J * G:
+        raise TypeError("C must be a %d x %d float64 tensor on the device of Z" % (J * G, J * G))
+    if C.stride(1) != 1 or C.stride(0) < J * G:
+        C = C.contiguous()
+    out = torch.empty(M, dtype=torch.float64, device=Z.device)
+    with _on(Z.device):
+        _lib.check(lib.rpgp_ski_quadform_f64(Z.data_ptr(), gp.data_ptr(), C.data_ptr(), out.data_ptr(), M,
+                                             Z.stride(0) if M > 1 else J, J, G, C.stride(0), _stream()), "rpgp_ski_quadform_f64")
+    return out

@@ -251,6 +251,11 @@ def build_parser():
                         "additive_rp and the weighted rp_poly / strictly_additive kinds with k = 1 and RBF sub-kernels")
     p.add_argument("--lowrank_posterior", action="store_true",
                    help="(rpgp) predict in closed form from the explicit features of the Chebyshev low-rank kernel where served")
+    p.add_argument("--ski_posterior", action="store_true",
+                   help="(rpgp) predict a `ski: true` model in closed form from Gram sums over its grid nodes where served: "
+                        "variances and test NLL at any number of test rows, no N x N* array")
+    p.add_argument("--ski_posterior_max_nodes", type=int, default=24576, metavar="N",
+                   help="(rpgp) largest J * grid_size served by --ski_posterior (default 24576)")
     p.add_argument("--lowrank_mll", action="store_true",
                    help="(rpgp) train on the closed-form marginal likelihood of the Chebyshev low-rank features where served")
     p.add_argument("--lowrank_max_rank", type=int, default=64, metavar="N",
@@ -414,6 +419,8 @@ def main(argv=None, rank_entry=None):
                 settings.lowrank_kernel(getattr(args, "lowrank_kernel", False)), \
                 settings.lowrank_posterior(getattr(args, "lowrank_posterior", False)), \
                 settings.lowrank_mll(getattr(args, "lowrank_mll", False)), \
+                settings.ski_posterior(getattr(args, "ski_posterior", False)), \
+                settings.ski_posterior_max_nodes(getattr(args, "ski_posterior_max_nodes", 24576)), \
                 settings.lowrank_max_rank(getattr(args, "lowrank_max_rank", 64)), \
                 settings.lowrank_panels(getattr(args, "lowrank_panels", False)), \
                 settings.fused_full(getattr(args, "fused_full", False)):

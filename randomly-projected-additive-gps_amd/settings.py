@@ -177,6 +177,13 @@ lowrank_posterior = _setting("lowrank_posterior", False, flag=True)
 # step runs exactly as with the setting off (lowrank_kernel then applies as before).  The weighted kinds (FamilyAdditiveOperator,
 # RBF, k = 1, every weight positive) are served on column forms, with the gradient of every component weight.
 lowrank_mll = _setting("lowrank_mll", False, flag=True)
+# prediction of an unsharded grid-interpolation (`ski: true`) model in closed form from Gram sums over its J G grid nodes
+# (ski_posterior.py): mean, variances, covariance and train / test log-densities at any number of test rows from
+# JG x JG float64 algebra, no CG and no N x N* array.  Served for J G <= ski_posterior_max_nodes, at most 4096 kept eigenpairs
+# (fewer than N), the node arrays within 25 % of the device memory, component weights >= 0, one rank; otherwise the strategy runs
+# as before and `strategy.ski_posterior_reason` says why.  Off (the default): nothing changes, bit for bit.
+ski_posterior = _setting("ski_posterior", False, flag=True)
+ski_posterior_max_nodes = _setting("ski_posterior_max_nodes", 24576)
 
 
 # the largest Chebyshev rank that lowrank_posterior, lowrank_mll (p) and lowrank_kernel (p and q) serve: 64 covers a half-width of the 1-D term of about 7.3

@@ -573,6 +573,9 @@ def train_exact_gp(trainX, trainY, testX, testY, kind, model_kwargs, train_kwarg
     if settings.lowrank_posterior.on():
         st = getattr(model, "prediction_strategy", None)
         model_metrics["lowrank_posterior_served"] = int(getattr(st, "lowrank", None) is not None)
+    if settings.ski_posterior.on():
+        st = getattr(model, "prediction_strategy", None)
+        model_metrics["ski_posterior_served"] = int(getattr(st, "ski_post", None) is not None)
     model_metrics["training_warnings"] = len(fit_warnings)
     model_metrics["testing_warning"] = "" if len(test_warnings) == 0 else test_warnings[-1].message
     model_metrics["state_dict_file"] = _save_state_dict(model)
